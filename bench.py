@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the STTM merge hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode batch|dropin]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode batch|dropin] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json metric): synth-v1 videos of 128 frames x 14x14 tokens x 1024 channels, fp32, in the
@@ -11,7 +11,9 @@ temporal merge (thr 0.55) -- the LLaVA-Video-7B / Video-MME "50 % budget" preset
 (incl. its host-visible token count) produced.  `--mode batch` (default): get_quadtree_features_batch, `--batch`
 independent videos per call, which the library deals out to its internal streams (stage-skewed; identical outputs);
 `--mode dropin`: get_quadtree_features, one video per call on one stream (the definition of `value` in rounds 1-4).
-Whichever mode the timed region does not run is measured next to it.  Videos are independent, so N GPUs each take
+A plain run sets up, warms up, times the K steps and prints the headline line; `--full` adds every other leg (the mode the
+timed region does not run, the threaded / ToMe / hook extensions, the configurations, the per-kernel roofline leg and the
+CPU baseline with its parity check), each of which `--no-*` can skip again.  Videos are independent, so N GPUs each take
 their own videos (weak scaling); the only collective is the final gather of the per-video token counts over RCCL
 (with --validate also the padded merged-token indices).
 
@@ -58,11 +60,16 @@ def parse():
     ap.add_argument("--mode", choices=("batch", "dropin"), default="batch",
                     help="what the timed region (`value`) runs: 'batch' = get_quadtree_features_batch, --batch videos per call, dealt out to "
                          "the library's internal streams (stage-skewed; identical outputs); 'dropin' = get_quadtree_features, one video per "
-                         "call on one stream (rounds 1-4's headline).  The other mode is always reported next to it.")
+                         "call on one stream (rounds 1-4's headline).  With --full the other mode is reported next to it.")
     ap.add_argument("--batch", type=int, default=96, help="videos per get_quadtree_features_batch call in 'batch' mode")
     ap.add_argument("--validate", action="store_true",
                     help="after the timed region, all-gather the padded merged-token indices of a sample of videos over the ranks "
                          "and check them against each rank's own recomputation")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the other mode, the extension legs, the configurations, the per-kernel roofline "
+                         "leg and the CPU baseline (each can be skipped with its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step to DIR/<name>.npy (float32 / float64, rank 0)")
     return ap.parse_args()
 
 
@@ -258,15 +265,62 @@ def run_configs(dev, rank, world, timed, log):
     return out
 
 
+DUMP_ROWS = 1 << 20          # --dump-outputs: per-row outputs of at most this many merged tokens (40 B each with their index)
+DUMP_FEATURE_ROWS = 4096     # ... and feature rows of at most this many (4 KiB each at C = 1024): < 64 MB in all
+
+
+def dump_outputs(path, step_counts, last_call):
+    """--dump-outputs: what the timed path returned to its caller in the last timed step, as .npy files.
+
+    step_counts: the merged-token count N' of every video of the last step.  last_call: the (features [N', C], num_patches [N'],
+    tlbr [N', 5]) triples of the step's LAST call -- the only results of the step still alive (the batch entry point writes every call
+    into the same caller-owned blocks).  Their rows, concatenated video after video, are the dumped rows; past DUMP_ROWS /
+    DUMP_FEATURE_ROWS of them a fixed seeded sample (sorted) stands for them, so equal outputs give equal files."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = [o[0].shape[0] for o in last_call]
+    total = sum(n)
+    off = [0]
+    for k in n:
+        off.append(off[-1] + k)
+
+    def sample(cap, seed):
+        if total <= cap:
+            return torch.arange(total)
+        return torch.randperm(total, generator=torch.Generator().manual_seed(seed))[:cap].sort().values
+
+    def gather(i, idx):                                   # rows idx of the concatenation of output i over the videos
+        parts = []
+        for v, o in enumerate(last_call):
+            sel = idx[(idx >= off[v]) & (idx < off[v + 1])] - off[v]
+            if sel.numel():
+                parts.append(o[i][sel.to(o[i].device)].cpu())
+        return torch.cat(parts)
+
+    rows, frows = sample(DUMP_ROWS, 1), sample(DUMP_FEATURE_ROWS, 2)
+    row_sum = torch.cat([o[0].double().sum(1).cpu() for o in last_call])[rows]
+    arrays = {"counts": torch.tensor(step_counts, dtype=torch.float64), "row_index": rows.double(),
+              "num_patches": gather(1, rows).float(), "tlbr": gather(2, rows).float(), "feature_row_sum": row_sum,
+              "feature_row_index": frows.double(), "features": gather(0, frows).float()}
+    nbytes = 0
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
+        nbytes += a.numel() * a.element_size()
+    assert nbytes <= 64e6, f"--dump-outputs wrote {nbytes / 1e6:.1f} MB"
+    return {"videos": len(step_counts), "videos_with_rows": len(n), "rows": total, "MB": round(nbytes / 1e6, 2)}
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ:
         if torch.cuda.is_available() and torch.cuda.device_count() < args.gpus:
             sys.exit(f"bench.py --gpus {args.gpus}: this node has {torch.cuda.device_count()} GPU(s)")
-        # plain `python bench.py --gpus N`: become the launcher of N ranks (one process per GPU, RCCL over xGMI)
+        # plain `python bench.py --gpus N`: start the launcher of N ranks (one process per GPU, RCCL over xGMI) as a child process --
+        # this one has already initialised the HIP runtime above, so it must not be replaced in place
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:]
-        os.execv(sys.executable, cmd)
+        import subprocess
+        sys.exit(subprocess.run(cmd).returncode)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -301,18 +355,21 @@ def main():
     torch.cuda.synchronize()
     log(f"pool of {P} videos ready")
 
+    last_call = [None]          # the results of the latest call of the step functions (what --dump-outputs writes)
+
     def run_step_dropin(s, sink):
         for v in range(V):
             x = pool[(s * V + v) % P]
             feat, npatch, tlbr = get_quadtree_features(x, thr, tthr, root)
             sink.append(feat.shape[0])
+        last_call[0] = [(feat, npatch, tlbr)]
 
     BATCH = max(1, args.batch)
 
     # caller-owned output blocks for the batch entry point (ABI v8 `out=`): allocated ONCE, reused by every call -- what a pipeline that
     # consumes a call's results before issuing the next one does; no 10 GB of worst-case rows per call through the allocator
     out_blocks = None
-    if args.mode == "batch" or not args.no_extensions:
+    if args.mode == "batch" or (args.full and not args.no_extensions):
         nb_ = min(BATCH, V)
         out_blocks = (torch.empty((nb_, T * H * W, C), device=dev), torch.empty((nb_, T * H * W), dtype=torch.int32, device=dev),
                       torch.empty((nb_, T * H * W, 5), dtype=torch.int32, device=dev))
@@ -321,6 +378,7 @@ def main():
         for b0 in range(0, V, BATCH):
             outs = get_quadtree_features_batch([pool[(s * V + v) % P] for v in range(b0, min(V, b0 + BATCH))], thr, tthr, root, out=out_blocks)
             sink.extend(o[0].shape[0] for o in outs)
+        last_call[0] = outs
 
     def barrier():
         if dist is not None:
@@ -334,6 +392,9 @@ def main():
     job = run_sharded_job(step_fn, K, Wm, V, rank, world, dev, dist, sync=torch.cuda, barrier_device_ids=[local_rank] if dist is not None else None)
     elapsed, videos, value, t_issue = job["elapsed_s"], job["videos"], job["value"], job["t_issue_s"]
     log(f"timed region ({args.mode}): {videos} videos in {elapsed:.4f} s = {value:.1f} videos/s (calls returned after {t_issue:.4f} s)")
+    if args.dump_outputs and rank == 0:
+        # before any other leg: the batch entry point's next call would overwrite the last call's results in out_blocks
+        log(f"dumped outputs: {dump_outputs(args.dump_outputs, job['counts'][-V:], last_call[0])}")
 
     def timed(fn, n_videos):
         torch.cuda.synchronize()
@@ -382,7 +443,7 @@ def main():
 
     # ---- extension legs (identical outputs; never the headline value) ---------------------------------------------------
     ext = {}
-    if not args.no_extensions:
+    if args.full and not args.no_extensions:
         KE = max(1, min(K, 4))
         # the mode the timed region did NOT run, same videos, KE steps
         if args.mode == "batch":
@@ -466,7 +527,7 @@ def main():
     # ---- hook leg: what the patched decoder forward does around the merge (quadtree_attn_monkey_patch.py:88-117) at the production
     #      shape: bf16 hidden states [1, 20 system + T*196 visual + 60 instruction tokens, 3584]; slice -> merge -> concat as the
     #      reference writes it (merge + torch.cat) against the fused form (the kernels write into the new hidden-state buffer) ----
-    if not args.no_extensions:
+    if args.full and not args.no_extensions:
         from sttm_amd import get_quadtree_features_into, patch_hooks
         Ch, n_sys, n_inst = 3584, 20, 60
         hs_pool = []
@@ -495,83 +556,85 @@ def main():
 
     # ---- configs leg: every BASELINE.json configuration + the production shapes, drop-in API, a few hundred ms each --------
     configs = None
-    if not args.no_configs:
+    if args.full and not args.no_configs:
         configs = run_configs(dev, rank, world, timed, log)
 
-    # ---- roofline leg: per-kernel HIP events recorded by the library on the launch stream, a bounded number of calls ----
-    ev = _lib.KernelEvents()
-    tot = [0.0] * 4
-    span = 0.0
-    nodes = merged = leafnodes = 0
-    calls = 0
-    n_prof = max(8, min(args.profile_calls, K * V))
-    for i in range(n_prof):
-        x = pool[i % P]
-        _, _, _, cnt, ctx = quadtree_merge_raw(x, thr, tthr, root, False, None, events=ev, return_ctx=True)
-        ms = ev.elapsed_ms()                 # waits for the call's last event
-        for k in range(4):
-            tot[k] += ms[k]
-        span += sum(ms)
-        dcnt = ctx[2][0].tolist()            # the diagnostic counters live in device memory (complete once the call has drained)
-        nodes += dcnt[_lib.CNT_NODES]
-        leafnodes += dcnt[_lib.CNT_LEAFNODES]
-        merged += cnt[_lib.CNT_OUT]
-        calls += 1
-    log("roofline leg done: " + ", ".join(f"{k}={t / calls:.4f} ms" for k, t in zip(KERNELS, tot)))
-    avg_ms = [t / calls for t in tot]
-    n_avg, m_avg, l_avg = nodes / calls, merged / calls, leafnodes / calls
-    es = 4
-    thw = T * H * W
-    kernel_bytes = [                                     # algorithmic (compulsory) bytes of each kernel per launch
-        es * C * thw + es * C * (n_avg - l_avg) + 24 * thw,   # read every token once, write every POOLED node once (1x1 nodes
-                                                              # stay in x), meta + inverse norm + default label / group size per token
-        es * C * n_avg,                                   # every node row read once (pairs share rows)
-        0.0,                                              # label kernel (k_col_labels): latency-bound, ~1 MB of edge lists and labels --
-                                                          # it has no bandwidth roofline; its time is in kernel_ms
-        es * C * n_avg + es * C * m_avg,                  # read node rows, write merged rows
-    ]
-    dom = max((0, 1, 3), key=lambda i: avg_ms[i])
-    pipeline_bytes = es * C * thw + es * C * m_avg + 24 * m_avg      # B per video
-    event_span_ms = span / calls                          # first event -> last event of a call WITH five event records in the stream:
-                                                          # longer than the undisturbed call (the records sit between the kernels)
-    wall_ms = elapsed / (K * V) * 1e3                     # the timed region itself: wall time per video on this GPU (includes the host)
-    dom_gbs = kernel_bytes[dom] / (avg_ms[dom] * 1e-3) / 1e9
-    pipe_gbs = pipeline_bytes / (wall_ms * 1e-3) / 1e9    # B over the time ONE video takes in the timed region
-    # HBM traffic from the PMC counters: only if the committed passes were taken on THIS build of the library
-    traffic = traffic_tag = traffic_where = None
-    pmc_path = os.path.join(REPO, "profiles", "pmc_traffic.json")
-    build_tag = _lib.build_tag()
-    if os.path.exists(pmc_path):
-        try:
-            rec = json.load(open(pmc_path))
-            if rec.get("workload") == f"T{T}_14x14x1024_f32_sttm_0.85_0.55" and rec.get("build_tag") == build_tag:
-                traffic = rec.get("hbm_bytes_per_video")
-                traffic_tag = rec.get("tag")
-                traffic_where = (f"builder's MI355X box (gpurun), profiles/{rec.get('tag')}_pmc_traffic.md, library build tag {rec.get('build_tag')} "
-                                 "== the tag of the library loaded now; NOT re-measured during this run (PMC passes need rocprofv3)")
-        except Exception:  # noqa: BLE001
-            traffic = None
-    roofline = {
-        "bound": "hbm", "scope": "pipeline: the whole merge of one video (SURVEY 8d: B / wall time per video of the timed region, i.e. B * value / "
-                                 "n_gpus); the dominant kernel's own figure is under dominant_kernel",
-        "achieved": round(pipe_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(pipe_gbs / HBM_PEAK_GBS, 4),
-        "frac_of_copy_rate": round(pipe_gbs / HBM_COPY_GBS, 4), "copy_rate_GBs": HBM_COPY_GBS,
-        "traffic": traffic, "traffic_profile": traffic_tag, "traffic_measured_on": traffic_where, "build_tag": build_tag,
-        "algorithmic_MB_per_video": round(pipeline_bytes / 1e6, 2), "wall_ms_per_video": round(wall_ms, 4),
-        "event_span_ms_per_video": round(event_span_ms, 4),
-        "dominant_kernel": {"kernel": KERNELS[dom], "achieved": round(dom_gbs, 1), "frac": round(dom_gbs / HBM_PEAK_GBS, 4),
-                            "frac_of_copy_rate": round(dom_gbs / HBM_COPY_GBS, 4),
-                            "algorithmic_MB": round(kernel_bytes[dom] / 1e6, 2), "ms": round(avg_ms[dom], 4)},
-        "kernel_ms": {k: round(v, 4) for k, v in zip(KERNELS, avg_ms)},
-        "kernel_ms_note": "HIP-event intervals recorded by the library on the launch stream during a separate leg; the event "
-                          "records themselves add ~1-2 us per interval -- profiles/*_rocprofv3_kernel_stats.md holds the undisturbed durations",
-        "kernel_algorithmic_MB": {k: round(b / 1e6, 2) for k, b in zip(KERNELS, kernel_bytes)},
-        "profiled_calls": calls,
-    }
+    roofline = None
+    if args.full:
+        # ---- roofline leg: per-kernel HIP events recorded by the library on the launch stream, a bounded number of calls ----
+        ev = _lib.KernelEvents()
+        tot = [0.0] * 4
+        span = 0.0
+        nodes = merged = leafnodes = 0
+        calls = 0
+        n_prof = max(8, min(args.profile_calls, K * V))
+        for i in range(n_prof):
+            x = pool[i % P]
+            _, _, _, cnt, ctx = quadtree_merge_raw(x, thr, tthr, root, False, None, events=ev, return_ctx=True)
+            ms = ev.elapsed_ms()                 # waits for the call's last event
+            for k in range(4):
+                tot[k] += ms[k]
+            span += sum(ms)
+            dcnt = ctx[2][0].tolist()            # the diagnostic counters live in device memory (complete once the call has drained)
+            nodes += dcnt[_lib.CNT_NODES]
+            leafnodes += dcnt[_lib.CNT_LEAFNODES]
+            merged += cnt[_lib.CNT_OUT]
+            calls += 1
+        log("roofline leg done: " + ", ".join(f"{k}={t / calls:.4f} ms" for k, t in zip(KERNELS, tot)))
+        avg_ms = [t / calls for t in tot]
+        n_avg, m_avg, l_avg = nodes / calls, merged / calls, leafnodes / calls
+        es = 4
+        thw = T * H * W
+        kernel_bytes = [                                     # algorithmic (compulsory) bytes of each kernel per launch
+            es * C * thw + es * C * (n_avg - l_avg) + 24 * thw,   # read every token once, write every POOLED node once (1x1 nodes
+                                                                  # stay in x), meta + inverse norm + default label / group size per token
+            es * C * n_avg,                                   # every node row read once (pairs share rows)
+            0.0,                                              # label kernel (k_col_labels): latency-bound, ~1 MB of edge lists and labels --
+                                                              # it has no bandwidth roofline; its time is in kernel_ms
+            es * C * n_avg + es * C * m_avg,                  # read node rows, write merged rows
+        ]
+        dom = max((0, 1, 3), key=lambda i: avg_ms[i])
+        pipeline_bytes = es * C * thw + es * C * m_avg + 24 * m_avg      # B per video
+        event_span_ms = span / calls                          # first event -> last event of a call WITH five event records in the stream:
+                                                              # longer than the undisturbed call (the records sit between the kernels)
+        wall_ms = elapsed / (K * V) * 1e3                     # the timed region itself: wall time per video on this GPU (includes the host)
+        dom_gbs = kernel_bytes[dom] / (avg_ms[dom] * 1e-3) / 1e9
+        pipe_gbs = pipeline_bytes / (wall_ms * 1e-3) / 1e9    # B over the time ONE video takes in the timed region
+        # HBM traffic from the PMC counters: only if the committed passes were taken on THIS build of the library
+        traffic = traffic_tag = traffic_where = None
+        pmc_path = os.path.join(REPO, "profiles", "pmc_traffic.json")
+        build_tag = _lib.build_tag()
+        if os.path.exists(pmc_path):
+            try:
+                rec = json.load(open(pmc_path))
+                if rec.get("workload") == f"T{T}_14x14x1024_f32_sttm_0.85_0.55" and rec.get("build_tag") == build_tag:
+                    traffic = rec.get("hbm_bytes_per_video")
+                    traffic_tag = rec.get("tag")
+                    traffic_where = (f"an MI355X, profiles/{rec.get('tag')}_pmc_traffic.md, library build tag {rec.get('build_tag')} "
+                                     "== the tag of the library loaded now; NOT re-measured during this run (PMC passes need rocprofv3)")
+            except Exception:  # noqa: BLE001
+                traffic = None
+        roofline = {
+            "bound": "hbm", "scope": "pipeline: the whole merge of one video (SURVEY 8d: B / wall time per video of the timed region, i.e. B * value / "
+                                     "n_gpus); the dominant kernel's own figure is under dominant_kernel",
+            "achieved": round(pipe_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(pipe_gbs / HBM_PEAK_GBS, 4),
+            "frac_of_copy_rate": round(pipe_gbs / HBM_COPY_GBS, 4), "copy_rate_GBs": HBM_COPY_GBS,
+            "traffic": traffic, "traffic_profile": traffic_tag, "traffic_measured_on": traffic_where, "build_tag": build_tag,
+            "algorithmic_MB_per_video": round(pipeline_bytes / 1e6, 2), "wall_ms_per_video": round(wall_ms, 4),
+            "event_span_ms_per_video": round(event_span_ms, 4),
+            "dominant_kernel": {"kernel": KERNELS[dom], "achieved": round(dom_gbs, 1), "frac": round(dom_gbs / HBM_PEAK_GBS, 4),
+                                "frac_of_copy_rate": round(dom_gbs / HBM_COPY_GBS, 4),
+                                "algorithmic_MB": round(kernel_bytes[dom] / 1e6, 2), "ms": round(avg_ms[dom], 4)},
+            "kernel_ms": {k: round(v, 4) for k, v in zip(KERNELS, avg_ms)},
+            "kernel_ms_note": "HIP-event intervals recorded by the library on the launch stream during a separate leg; the event "
+                              "records themselves add ~1-2 us per interval -- profiles/*_rocprofv3_kernel_stats.md holds the undisturbed durations",
+            "kernel_algorithmic_MB": {k: round(b / 1e6, 2) for k, b in zip(KERNELS, kernel_bytes)},
+            "profiled_calls": calls,
+        }
 
     # ---- CPU baseline leg (rank 0, N = 1 only): the oracle on a bounded sample of the same workload -------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         from oracle import sttm_oracle as O
         host = host_cpu_facts()
         ncpu = host["logical_cpus"]          # (the CPUs this process may run on: what torch can use, and what cpu_baseline reports)

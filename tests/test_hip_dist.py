@@ -82,7 +82,7 @@ def test_two_ranks_over_rccl_when_the_box_has_two_gpus(tmp_path):
 def test_bench_validate_mode_under_torchrun():
     """bench.py as the driver launches it (torchrun, one rank here), small sizes, with the index gather of --validate."""
     r = _torchrun(1, [os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--videos-per-step", "8", "--frames", "16",
-                      "--profile-calls", "8", "--no-cpu-baseline", "--no-extensions", "--no-configs", "--validate"])
+                      "--profile-calls", "8", "--full", "--no-cpu-baseline", "--no-extensions", "--no-configs", "--validate"])
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["validate"]["cross_rank_index_match"] is True
@@ -104,8 +104,47 @@ def test_bench_fails_fast_when_the_node_has_fewer_gpus_than_asked_for():
     assert r.returncode != 0 and f"this node has {n} GPU" in (r.stdout + r.stderr)
     # the value_definition / both-definitions fields of the JSON line: a tiny run
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "1", "--warmup", "1", "--videos-per-step", "16", "--frames", "16",
-                        "--batch", "8", "--profile-calls", "8", "--no-cpu-baseline", "--no-configs"], capture_output=True, text=True, timeout=600)
+                        "--batch", "8", "--profile-calls", "8", "--full", "--no-cpu-baseline", "--no-configs"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert "batch entry point" in line["value_definition"] and line["value_batch_entry_point"] == line["value"]
     assert line["value_one_call_per_video"] == line["dropin_one_call_per_video"]["value"] > 0
+
+
+def test_bench_plain_run_dumps_what_the_timed_path_returned(tmp_path):
+    """A plain run prints the headline line only (the other legs are behind --full); --dump-outputs writes the last timed step's
+    results, identical from run to run and equal to one get_quadtree_features call per video of the step's last call."""
+    import numpy as np
+    import torch
+    from sttm_amd import get_quadtree_features
+    from sttm_amd.synth import synth_video
+    T, V, B, P = 16, 16, 8, 8
+    dumps = []
+    for k in range(2):
+        d = tmp_path / f"dump{k}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "2", "--warmup", "1", "--videos-per-step", str(V),
+                            "--frames", str(T), "--batch", str(B), "--pool", str(P), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 2 and line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "videos/s"
+        assert line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["roofline"] is None and line["cpu_baseline"] is None
+        assert not {"configs", "dropin_one_call_per_video", "tome_extension", "hook_extension", "index_match"} & set(line)
+        arrays = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(a.nbytes for a in arrays.values()) <= 64e6
+        dumps.append(arrays)
+    assert dumps[0].keys() == dumps[1].keys() and all(np.array_equal(dumps[0][n], dumps[1][n]) for n in dumps[0])
+    a = dumps[0]
+    # the step's last call: videos V - B .. V - 1 of step 1, i.e. pool entries (V + v) % P of the seeded device-generated pool
+    dev = torch.device("cuda", 0)
+    outs = [get_quadtree_features(synth_video(T, 1024, 14, 14, seed=100000 + (V + v) % P, device=dev, gen_device=dev), 0.85, 0.55, 1)
+            for v in range(V - B, V)]
+    assert a["counts"].shape == (V,) and list(a["counts"][V - B:]) == [o[0].shape[0] for o in outs]
+    feat = torch.cat([o[0] for o in outs]).cpu()
+    assert np.array_equal(a["row_index"], np.arange(feat.shape[0]))
+    assert np.array_equal(a["num_patches"], torch.cat([o[1] for o in outs]).cpu().float().numpy())
+    assert np.array_equal(a["tlbr"], torch.cat([o[2] for o in outs]).cpu().float().numpy())
+    assert np.array_equal(a["feature_row_sum"], torch.cat([o[0].double().sum(1) for o in outs]).cpu().numpy())
+    assert np.array_equal(a["features"], feat[torch.from_numpy(a["feature_row_index"]).long()].numpy())

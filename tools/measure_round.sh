@@ -4,7 +4,7 @@
 set -u
 TAG=${1:-m}; shift || true
 mkdir -p gpurun_out
-B="python bench.py --steps 3 --warmup 1 --videos-per-step 512 --no-cpu-baseline --profile-calls 256"
+B="python bench.py --full --steps 3 --warmup 1 --videos-per-step 512 --no-cpu-baseline --profile-calls 256"
 $B > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err
 for V in "$@"; do
     N=$(echo "$V" | tr ' =' '__')
