@@ -264,6 +264,12 @@ int sttm_quadtree_merge_batch(int n_videos, const void* const* x, int64_t stride
  *                 (v_mfma_f32_32x32x2_f32), 2.9x slower; 3 / 4: force the 128-tile / 256-tile kernel with four terms, 5 / 6 with three (tests);
  *                 7: the FOUR-WAVE form of the 256-tile kernel, three terms, also for 16-bit inputs (128 x 128 wave tiles, one wave per SIMD,
  *                 the 256 accumulators in literally named AGPRs; round 6 -- no faster than the eight-wave form)
+ *   "wide_lanes"  the channel-tiled spatial stage (csrc/spatial_wide.inc: the row cut into chunks of at most 1024 lanes, one workgroup per
+ *                 (frame, root cell, chunk), partial statistics summed in chunk order by a second pass that takes the decisions, a third
+ *                 that writes the node rows).  0 (default): only for token rows of more than 1024 packs (fp32 C > 4096, 16-bit C > 8192,
+ *                 or narrower packs forced by the alignment); 256 / 512 / 1024: chunks of exactly that many lanes, and the tiled form
+ *                 also for every row with 16-byte packs (tests / A-B).  Same node set and feature bits; the statistics are summed in
+ *                 another order.  Other values: STTM_ERR_ARG.
  *   "tome_flat"   256-tile ToMe match kernels: 1 (default) spread all tile products evenly over one workgroup per CU when that
  *                 shortens the per-CU critical path against the best per-a-tile split (69 x 69 tiles at T = 180: 19 instead of 23
  *                 products per workgroup), 0 never, 2 always.  Same scores, same first-maximum argmax.

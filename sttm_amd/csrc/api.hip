@@ -25,7 +25,7 @@ int fail(int code, const char* fmt, ...) {
 // None of them changes results.
 struct Config {
     int pairs_seg, pairs_nt, pairs_var, k1_var, k1_split, no_dense, gm_split, label_nt, vec16, vec32, fold_kb, fold_labels, no_fuse, force_gmem_labels, tome_split, tome_flat,
-        batch_streams, batch_sub, col_walk, col_frames, col_cap, col_pb, col_abl, pair_vec;
+        batch_streams, batch_sub, col_walk, col_frames, col_cap, col_pb, col_abl, pair_vec, wide_lanes;
 };
 int env_int(const char* name, int dflt) {
     const char* e = getenv(name);
@@ -63,6 +63,9 @@ Config& config() {
 #else
         d.col_abl = 0;
 #endif
+        // the channel-tiled spatial stage (spatial_wide.inc): 0 = only for rows wider than one workgroup; 256 / 512 / 1024 = chunks of that
+        // many lanes, and the tiled form also for every row with 16-byte packs (tests / A-B)
+        d.wide_lanes = env_int("STTM_WIDE_LANES", 0);
         d.pair_vec = env_int("STTM_PAIR_VEC", 0);          // 0 = the column walk's width where it could run (see merge_group); -1 = the row kernels' width (rounds 1-5)
         return d;
     }();
@@ -252,6 +255,21 @@ int pick_vec(int C, int dtype, const void* x, int64_t sT, int64_t sH, int64_t sW
     return 0;
 }
 
+// Pack width of a row that fits no workgroup (the channel-tiled spatial stage): the widest of pick_vec's candidates that the
+// channel count and the alignment allow, 16-byte packs first; 0 if none.
+int pick_vec_tiled(int C, int dtype, const void* x, int64_t sT, int64_t sH, int64_t sW) {
+    const int eb = elem_bytes(dtype);
+    const int cands_f32[] = {4, 2, 1}, cands_16[] = {8, 4, 2};
+    const int* cands = dtype == STTM_F32 ? cands_f32 : cands_16;
+    for (int k = 0; k < 3; ++k) {
+        const int v = cands[k];
+        const size_t ab = (size_t)v * eb;
+        if (C % v || reinterpret_cast<uintptr_t>(x) % ab || (sT * eb) % ab || (sH * eb) % ab || (sW * eb) % ab) continue;
+        return v;
+    }
+    return 0;
+}
+
 // `sim_f32 >= thr_f32`  <=>  `sim >= lo` with lo = the midpoint below the fp32 threshold (exclusive when the tie would round
 // down to the predecessor, i.e. when the threshold's mantissa is odd); returned as lo * |lo| for the division-free test.
 double thr_lo_sq_of(float thr) {
@@ -386,7 +404,9 @@ int merge_group(int nv, const void* const* x, int64_t stride_t, int64_t stride_c
     const void* x_align = reinterpret_cast<const void*>(all_bits);      // the least aligned of the inputs decides the pack width
     int nt = 0;
     if (int rc = check_frame_addressing(pool ? pool->src_h : H, pool ? pool->src_w : W, C, (int)elem_bytes(dtype), stride_h, stride_w, stride_t)) return rc;
-    const int vec = pick_vec(C, dtype, x_align, stride_t, stride_h, stride_w, &nt, head_dim == 0 && !pool);
+    const Config& cfg = config();
+    const int wide_lanes = (cfg.wide_lanes == 256 || cfg.wide_lanes == 512 || cfg.wide_lanes == 1024) ? cfg.wide_lanes : 0;
+    int vec = pick_vec(C, dtype, x_align, stride_t, stride_h, stride_w, &nt, head_dim == 0 && !pool && !wide_lanes);
     if (pool) {
         // the fused pooled-leaf load exists for the shape the production presets use: 3-level trees, 16-byte packs, whole-vector cosine
         if (p.dims.n_level != 3 || head_dim != 0 || vec * (int)elem_bytes(dtype) != 16 || H > sttm::kPoolMaxSide || W > sttm::kPoolMaxSide)
@@ -394,7 +414,33 @@ int merge_group(int nv, const void* const* x, int64_t stride_t, int64_t stride_c
                         "aligned rows with C %% %d == 0, a pooled grid of at most %d x %d; pool with sttm_pool2d and call sttm_quadtree_merge instead",
                         p.dims.n_level, 16 / (int)elem_bytes(dtype), sttm::kPoolMaxSide, sttm::kPoolMaxSide);
     }
-    if (!vec) return fail(STTM_ERR_UNSUPPORTED, "C=%d with this alignment does not fit one workgroup (need C/vec <= 1024 lanes)", C);
+    // Rows of more than 1024 packs run the channel-tiled spatial stage (spatial_wide.inc), as does every row with 16-byte packs when
+    // wide_lanes forces it.  Chunks: all of one width, a multiple of 64 lanes, at most 256 (wide_lanes: that many, 4-level trees at most
+    // 512).  Measured on fp32 C = 8192, T = 128, 14 x 14 (2048 lanes): whole call 663 us with 256-lane chunks, 686 with 512, 741 with
+    // 1024 -- four-wave workgroups sum their per-wave statistics faster and fill the CUs more evenly.
+    bool tiled = false;
+    int tiled_nt = 0, nchunk = 0;
+    if (!vec) {
+        vec = pick_vec_tiled(C, dtype, x_align, stride_t, stride_h, stride_w);
+        tiled = vec != 0;
+    } else if (wide_lanes && !nodes && !pool && vec * (int)elem_bytes(dtype) == 16) {
+        tiled = true;
+    }
+    if (!vec) return fail(STTM_ERR_UNSUPPORTED, "C=%d: no channel pack divides the channel count at this alignment", C);
+    if (tiled && !nodes) {
+        if (p.dims.n_level > 4)
+            return fail(STTM_ERR_UNSUPPORTED, "rows of %d channels run the channel-tiled spatial stage, which takes trees of at most 4 levels "
+                        "(this grid and root_level give %d; rows of at most 1024 %d-byte packs take any depth)", C, p.dims.n_level,
+                        4 * (int)elem_bytes(dtype));
+        const int lanes = (C + vec - 1) / vec;
+        const int cap = sttm::wide_max_lanes(p.dims.n_level);
+        const int max_nt = wide_lanes ? (wide_lanes < cap ? wide_lanes : cap) : 256;
+        nchunk = (lanes + max_nt - 1) / max_nt;
+        tiled_nt = wide_lanes ? max_nt : ((lanes + nchunk - 1) / nchunk + 63) / 64 * 64;
+        // the statistics table of the tiled stage lives at the start of S (written before, and read before, any node row)
+        if (sttm::wide_stats_floats(T, p.dims, nchunk) * sizeof(float) > (size_t)p.N * C * elem_bytes(dtype))
+            return fail(STTM_ERR_UNSUPPORTED, "C=%d: the tiled spatial stage's statistics table does not fit the node scratch", C);
+    }
     int n_head = 0, head_lanes = 0;
     if (head_dim > 0) {
         // one head = head_dim / vec adjacent lanes: must be a power of two that fits a wave
@@ -404,7 +450,6 @@ int merge_group(int nv, const void* const* x, int64_t stride_t, int64_t stride_c
             return fail(STTM_ERR_UNSUPPORTED, "head_dim / pack width = %d lanes: need a power of two <= 64", head_lanes);
         n_head = C / head_dim;
     }
-    const Config& cfg = config();
     Buffers b;
     carve_all(p, T, H, W, C, dtype, reinterpret_cast<char*>(workspace), &b);
     sttm::SpatialArgs sa;
@@ -461,7 +506,7 @@ int merge_group(int nv, const void* const* x, int64_t stride_t, int64_t stride_c
         cw.abl = cfg.col_abl;
         if (cap < 4 && cfg.col_cap <= 0) col_shape = false;
     }
-    const bool col_walk = col_shape && (cfg.col_walk >= 2 || (cfg.col_walk == 1 && nv > 1));
+    const bool col_walk = col_shape && !tiled && (cfg.col_walk >= 2 || (cfg.col_walk == 1 && nv > 1));
     ta.pair_vec = cfg.pair_vec > 0 ? cfg.pair_vec : ((col_shape && cfg.pair_vec == 0) ? vec16 : ta.vec);
     sttm::pairs_shape(T, p.R, cfg.fold_labels && !slow_ver, cfg.pairs_seg, cfg.pairs_nt, &ta.pairs_seg, &ta.pairs_nt);
     ta.pairs_var = cfg.pairs_var;
@@ -515,7 +560,7 @@ int merge_group(int nv, const void* const* x, int64_t stride_t, int64_t stride_c
     void* tops = (n_head == 0 && p.dims.n_level >= split_from) ? b.tops : nullptr;
     // the one-workgroup form of a 6-level tree (per-head cosine, k1_split = -1) keeps 2735 partial statistics per wave in LDS
     // (10.7 KB): at most 12 waves fit next to the other tables
-    if (!tops && p.dims.n_level >= 6 && nt > 768)
+    if (!tops && !tiled && p.dims.n_level >= 6 && nt > 768)
         return fail(STTM_ERR_UNSUPPORTED, "a %d-level tree with %d lanes per token row does not fit the LDS in the one-workgroup form "
                     "(per-head cosine or k1_split = -1; 6-level trees: <= 768 lanes, i.e. fp32 C <= 3072, 16-bit C <= 6144)", p.dims.n_level, nt);
     if (nodes) {
@@ -524,6 +569,9 @@ int merge_group(int nv, const void* const* x, int64_t stride_t, int64_t stride_c
     } else if (pool) {
         if ((e = sttm::launch_spatial_pooled(sa, bp, nv, dtype, nt, stream)) != hipSuccess)
             return fail(STTM_ERR_LAUNCH, "spatial kernel (pooled input): %s", hipGetErrorString(e));
+    } else if (tiled) {
+        if ((e = sttm::launch_spatial_wide(sa, bp, nv, dtype, vec, tiled_nt, nchunk, stream)) != hipSuccess)
+            return fail(STTM_ERR_LAUNCH, "spatial kernel (channel-tiled): %s", hipGetErrorString(e));
     } else if (col_walk) {
         cw.edges = ta.edges; cw.edge_cnt = ta.edge_cnt; cw.cand_cnt = ta.cand_cnt; cw.ecap = ta.ecap; cw.temporal_thresh = temporal_thresh;
         if ((e = sttm::launch_spatial_col(sa, bp, cw, nv, dtype, col_nt, stream)) != hipSuccess)
@@ -647,6 +695,11 @@ int sttm_configure(const char* key, int value) {
 #endif
         {"pair_vec", &c.pair_vec},
     };
+    if (!strcmp(key, "wide_lanes")) {
+        if (value != 0 && value != 256 && value != 512 && value != 1024) return fail(STTM_ERR_ARG, "wide_lanes must be 0, 256, 512 or 1024 (got %d)", value);
+        c.wide_lanes = value;
+        return STTM_OK;
+    }
     for (auto& k : keys)
         if (!strcmp(key, k.name)) { *k.slot = value; return STTM_OK; }
     return fail(STTM_ERR_ARG, "unknown configuration key '%s'", key);

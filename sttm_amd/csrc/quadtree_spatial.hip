@@ -15,6 +15,17 @@ hipError_t launch_spatial(const SpatialArgs& a, const BatchPtrs& bp, int n_video
     return hipErrorInvalidValue;
 }
 
+template <typename T, bool PERHEAD>
+hipError_t launch_spatial_wide_t(const SpatialArgs& a, const BatchPtrs& bp, int n_videos, int vec, int nt, int nchunk, hipStream_t stream);
+
+hipError_t launch_spatial_wide(const SpatialArgs& a, const BatchPtrs& bp, int n_videos, int dtype, int vec, int nt, int nchunk, hipStream_t stream) {
+    const bool ph = a.n_head > 0;
+    if (dtype == STTM_F32) return ph ? launch_spatial_wide_t<float, true>(a, bp, n_videos, vec, nt, nchunk, stream) : launch_spatial_wide_t<float, false>(a, bp, n_videos, vec, nt, nchunk, stream);
+    if (dtype == STTM_BF16) return ph ? launch_spatial_wide_t<bf16_t, true>(a, bp, n_videos, vec, nt, nchunk, stream) : launch_spatial_wide_t<bf16_t, false>(a, bp, n_videos, vec, nt, nchunk, stream);
+    if (dtype == STTM_F16) return ph ? launch_spatial_wide_t<f16_t, true>(a, bp, n_videos, vec, nt, nchunk, stream) : launch_spatial_wide_t<f16_t, false>(a, bp, n_videos, vec, nt, nchunk, stream);
+    return hipErrorInvalidValue;
+}
+
 template <typename T>
 hipError_t launch_apply_t(const SpatialArgs& a, int vec, int nt, hipStream_t stream);
 

@@ -1,0 +1,6 @@
+// Explicit instantiation of the channel-tiled spatial stage (spatial_wide.inc) for one (dtype, per-head) combination.
+#include "spatial_wide.inc"
+
+namespace sttm {
+template hipError_t launch_spatial_wide_t<bf16_t, false>(const SpatialArgs&, const BatchPtrs&, int, int, int, int, hipStream_t);
+}  // namespace sttm

@@ -101,6 +101,14 @@ inline size_t split_ufeat_bytes(int T, const LevelDims& d, int C, int elem_bytes
 // whole-vector cosine only); tops = [T][h_block_level][w_block_level][C] elements of the input dtype per video, inside the workspace
 hipError_t launch_spatial(const SpatialArgs& a, const BatchPtrs& bp, int n_videos, int dtype, int vec, int nt, hipStream_t stream, void* tops = nullptr);
 hipError_t launch_node_apply(const SpatialArgs& a, int dtype, int vec, int nt, hipStream_t stream);
+// The channel-tiled spatial stage (spatial_wide.inc) for rows wider than one workgroup: nchunk chunks of nt lanes (a multiple of 64) per
+// token row, trees of at most 4 levels.  Its statistics table, T * R * nchunk * NSTAT floats, sits at the start of S (wide_stats_floats).
+hipError_t launch_spatial_wide(const SpatialArgs& a, const BatchPtrs& bp, int n_videos, int dtype, int vec, int nt, int nchunk, hipStream_t stream);
+inline int wide_max_lanes(int n_level) { return n_level >= 4 ? 512 : 1024; }      // lanes per chunk (k_wide_stats' launch bounds)
+inline size_t wide_stats_floats(int T, const LevelDims& d, int nchunk) {
+    const int D = d.n_level;
+    return (size_t)T * d.h[0] * d.w[0] * nchunk * (depth_base(D) + 4 * depth_base(D - 1) + D);
+}
 // The column-walk spatial stage (spatial_col.inc, round 6; launch sets of several videos): one workgroup per (root cell, chunk of
 // `frames` frames) that also runs the pair stage on rows kept in LDS.  The pointers are TemporalArgs' (video 0; shifted per video).
 struct ColWalkArgs {

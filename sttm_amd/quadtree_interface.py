@@ -664,8 +664,10 @@ def get_quadtree_features_from_pooled_input(image_feature, threshold, temporal_t
     # rows below 4 KB (two waves per root cell) do not keep enough source rows in flight: measured bf16 C = 1024 112 us fused against
     # 105 us in two steps, C = 2048 158 / 161, fp32 C = 1024 134 / 157, bf16 C = 3584 253 / 263 (tools/bench_pool_fused.py); force=True
     # in the tests runs the fused kernel on every shape it supports
+    # (rows of more than 1024 16-byte packs -- fp32 C > 4096, 16-bit C > 8192 -- run the channel-tiled spatial stage, which has no
+    # fused pooled-leaf form: they take the two steps)
     fused = (head_dim is None and (mode == "bilinear" or int(stride) == 2) and (C * eb) % 16 == 0 and x.data_ptr() % 16 == 0
-             and max(H, W) <= 64 and lib.sttm_quadtree_num_levels(H, W, int(root_level)) == 3 and (force_fused or C * eb >= 4096))
+             and C * eb <= 16 * 1024 and max(H, W) <= 64 and lib.sttm_quadtree_num_levels(H, W, int(root_level)) == 3 and (force_fused or C * eb >= 4096))
     if not fused:
         from .upstream import get_2dPool
         pooled = get_2dPool(x, stride=stride, width=side_w, mode=mode)
