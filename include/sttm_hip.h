@@ -392,6 +392,37 @@ size_t sttm_octree_workspace_bytes(int n_cubes, int side, int C, int dtype, int 
 int sttm_octree_build(const void* x, int n_cubes, int side, int C, int dtype, float threshold, int root_level,
                       void* workspace, size_t workspace_bytes, void* feat_out, int32_t* count_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ragged pack of a batched quadtree hook: B left-padded prompt rows, each with ONE video merged to N'_b rows, become the
+ * compact left-padded block the decoder layers after the merge read.  Row b of the input (all indices count from the row's
+ * first valid token, pad_b columns in):  system [0, start) | video [start, start + length) | instruction [start + length, ..).
+ *   hidden    [B, L, C] layer output, channel stride 1, token / batch strides in ELEMENTS
+ *   feat[b]   [>= N'_b, C] contiguous merged rows of video b (e.g. the per-video blocks of sttm_quadtree_merge_batch)
+ *   tlbr[b]   [>= N'_b, 5] int32 (t, y1, x1, y2, x2) of those rows
+ *   geom      [B][STTM_PACK_GEOM] int32 host table: pad_b, start_b, length_b, N'_b, T_b, H_b, W_b (length_b == T_b * H_b * W_b)
+ *   out       [B, Lout, C] contiguous, Lout >= every L'_b = L - pad_b - length_b + N'_b.  Row b: Lout - L'_b zero rows, then
+ *             system, the N'_b merged rows, instruction
+ *   mask_out  [B, Lout] int64: 0 on the pad columns, 1 on the rest
+ *   idx_out[b] [>= N'_b] int32: t * H * W + y1 * W + x1 of every merged row (merged_token_1d_idx)
+ *   pos_mode  STTM_PACK_POS_NONE; STTM_PACK_POS_TRUNCATE: pos_out [B, Lout] int64, valid column j of row b gets
+ *             pos_in[b * pos_stride_b + pad_b + j] (the truncation of quadtree_attn_monkey_patch.py:114);
+ *             STTM_PACK_POS_GATHER3: pos_out [3, B, Lout] int64, the 3-D mRoPE ids of system / instruction tokens kept and those of
+ *             the merged rows gathered by idx (token_merging_qwen2vl_monkey_patch/quadtree_attn_monkey_patch.py:109-113), read at
+ *             pos_in[a * pos_stride_a + b * pos_stride_b + column].  Pad columns get 1.
+ * Bytes are copied, not converted: the rows are bit-identical to their sources.  float32, bfloat16, float16; 16-byte packs when
+ * every row start allows them, narrower otherwise.  One launch per STTM_BATCH_MAX rows on `stream`, no workspace, no host
+ * synchronisation.  STTM_ERR_ARG for a geometry that does not fit L / Lout or a missing pointer.
+ * ------------------------------------------------------------------------------------------------ */
+#define STTM_PACK_GEOM 7
+#define STTM_PACK_POS_NONE 0
+#define STTM_PACK_POS_TRUNCATE 1
+#define STTM_PACK_POS_GATHER3 2
+int sttm_pack_merged_batch(int B, int C, int dtype, const void* hidden, int64_t hidden_stride_b, int64_t hidden_stride_t, int L,
+                           const void* const* feat, const int32_t* const* tlbr, const int32_t* geom, int Lout,
+                           void* out, int64_t* mask_out, int32_t* const* idx_out,
+                           int pos_mode, const int64_t* pos_in, int64_t pos_stride_a, int64_t pos_stride_b, int64_t* pos_out,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,8 @@ OVF_BARRIER_TIMEOUT = 64   # STTM_OVF_BARRIER_TIMEOUT
 EVENT_SLOTS = 5            # STTM_EVENT_SLOTS
 BATCH_MAX = 16             # STTM_BATCH_MAX
 EARLY_SLOTS = 64           # STTM_EARLY_SLOTS
+PACK_GEOM = 7              # STTM_PACK_GEOM
+PACK_POS_NONE, PACK_POS_TRUNCATE, PACK_POS_GATHER3 = 0, 1, 2
 
 # every symbol include/sttm_hip.h declares, with its ctypes signature
 _vp, _i, _i64, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
@@ -57,6 +59,7 @@ SIGNATURES = {
     "sttm_octree_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sttm_octree_build": (_i, [_vp, _i, _i, _i, _i, ctypes.c_float, _i, _vp, _sz, _vp, _vp, _vp]),
     "sttm_resize_nearest": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sttm_pack_merged_batch": (_i, [_i, _i, _i, _vp, _i64, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp]),
 }
 
 

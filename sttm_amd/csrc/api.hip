@@ -1017,6 +1017,81 @@ int sttm_resize_nearest(const void* x, int T, int H, int W, int C, int dtype, in
     return STTM_OK;
 }
 
+int sttm_pack_merged_batch(int B, int C, int dtype, const void* hidden, int64_t hidden_stride_b, int64_t hidden_stride_t, int L,
+                           const void* const* feat, const int32_t* const* tlbr, const int32_t* geom, int Lout,
+                           void* out, int64_t* mask_out, int32_t* const* idx_out,
+                           int pos_mode, const int64_t* pos_in, int64_t pos_stride_a, int64_t pos_stride_b, int64_t* pos_out,
+                           void* stream_) {
+    if (B < 1 || C < 1 || L < 1 || Lout < 1) return fail(STTM_ERR_ARG, "pack: B, C, L and Lout must be >= 1");
+    if (dtype < 0 || dtype > 2) return fail(STTM_ERR_ARG, "bad dtype");
+    if (!hidden || !feat || !tlbr || !geom || !out || !mask_out || !idx_out) return fail(STTM_ERR_ARG, "pack: null pointer argument");
+    if (pos_mode < STTM_PACK_POS_NONE || pos_mode > STTM_PACK_POS_GATHER3) return fail(STTM_ERR_ARG, "pack: bad pos_mode %d", pos_mode);
+    if (pos_mode != STTM_PACK_POS_NONE && (!pos_in || !pos_out)) return fail(STTM_ERR_ARG, "pack: pos_mode %d needs pos_in and pos_out", pos_mode);
+    if (pos_stride_a < 0 || pos_stride_b < 0) return fail(STTM_ERR_ARG, "pack: negative position stride");
+    if (hidden_stride_t < C || hidden_stride_b < (int64_t)L * hidden_stride_t)
+        return fail(STTM_ERR_ARG, "pack: hidden strides (%lld, %lld) overlap rows of [%d, %d, %d]", (long long)hidden_stride_b,
+                    (long long)hidden_stride_t, B, L, C);
+    const int64_t eb = elem_bytes(dtype);
+    const int64_t row_bytes = (int64_t)C * eb;
+    if (row_bytes > 0x7fffffff) return fail(STTM_ERR_UNSUPPORTED, "pack: rows of %d channels", C);
+    // the widest word every row start allows: pointers, strides and the row length
+    uintptr_t align = reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(out) | (uintptr_t)row_bytes
+                      | (uintptr_t)(hidden_stride_b * eb) | (uintptr_t)(hidden_stride_t * eb);
+    for (int b = 0; b < B; ++b) {
+        const int32_t* g = geom + (size_t)b * STTM_PACK_GEOM;
+        const int pad = g[0], start = g[1], length = g[2], n = g[3], T = g[4], H = g[5], W = g[6];
+        if (!feat[b] || !tlbr[b] || !idx_out[b]) return fail(STTM_ERR_ARG, "pack: null pointer for row %d", b);
+        if (pad < 0 || start < 0 || length < 1 || n < 1 || n > length || T < 1 || H < 1 || W < 1 || (int64_t)T * H * W != length)
+            return fail(STTM_ERR_ARG, "pack: row %d has pad %d, start %d, length %d, N' %d, grid %d x %d x %d", b, pad, start, length, n, T, H, W);
+        if ((int64_t)pad + start + length > L)
+            return fail(STTM_ERR_ARG, "pack: row %d (pad %d + start %d + length %d) is longer than L = %d", b, pad, start, length, L);
+        if ((int64_t)L - pad - length + n > Lout)
+            return fail(STTM_ERR_ARG, "pack: row %d packs to %lld columns, Lout = %d", b, (long long)L - pad - length + n, Lout);
+        align |= reinterpret_cast<uintptr_t>(feat[b]);
+    }
+    int pack = 16;
+    while (pack > 2 && (align % pack)) pack >>= 1;
+    if (align % pack) return fail(STTM_ERR_UNSUPPORTED, "pack: rows are not aligned to their element size");
+    hipStream_t stream = reinterpret_cast<hipStream_t>(stream_);
+    sttm::PackArgs a{};
+    a.hidden = static_cast<const char*>(hidden);
+    a.out = static_cast<char*>(out);
+    a.mask = mask_out;
+    a.pos_in = pos_in;
+    a.pos_out = pos_out;
+    a.hid_stride_b = hidden_stride_b * eb;
+    a.hid_stride_t = hidden_stride_t * eb;
+    a.pos_stride_a = pos_stride_a;
+    a.pos_stride_b = pos_stride_b;
+    a.B = B;
+    a.Lout = Lout;
+    a.row_bytes = (int)row_bytes;
+    a.packs = (int)(row_bytes / pack);
+    a.pos_mode = pos_mode;
+    // one launch per kBatchMax rows: the row descriptors travel in the kernel arguments
+    for (int b0 = 0; b0 < B; b0 += sttm::kBatchMax) {
+        const int nr = B - b0 < sttm::kBatchMax ? B - b0 : sttm::kBatchMax;
+        a.b0 = b0;
+        for (int r = 0; r < nr; ++r) {
+            const int32_t* g = geom + (size_t)(b0 + r) * STTM_PACK_GEOM;
+            sttm::PackRow& d = a.rows[r];
+            d.feat = static_cast<const char*>(feat[b0 + r]);
+            d.tlbr = tlbr[b0 + r];
+            d.idx = idx_out[b0 + r];
+            d.pad_in = g[0];
+            d.start = g[1];
+            d.length = g[2];
+            d.n = g[3];
+            d.hw = g[5] * g[6];
+            d.w = g[6];
+            d.pad_out = Lout - (L - g[0] - g[2] + g[3]);
+        }
+        hipError_t e = sttm::launch_pack_merged(a, nr, pack, stream);
+        if (e != hipSuccess) return fail(STTM_ERR_LAUNCH, "pack kernel: %s", hipGetErrorString(e));
+    }
+    return STTM_OK;
+}
+
 static inline int dycoke_pairs(int T) { return T / 2 + (T > 4 ? (T - 4 + 3) / 4 : 0); }
 
 size_t sttm_dycoke_workspace_bytes(int T, int P, int k) {

@@ -224,6 +224,29 @@ int tome_split_mode();       // 0 = fp32-input MFMA match kernel; > 0 = fp16 two
 
 hipError_t launch_pool2d(const void* x, void* out, int T, int H, int W, int C, int OH, int OW, int stride, int mode, int dtype,
                          hipStream_t stream);
+
+// Ragged pack of the batched hook (pack.hip, sttm_pack_merged_batch).  Byte offsets and host-validated geometry only: the kernel
+// finds a column's source with three comparisons, no division.
+struct PackRow {
+    const char* feat;         // merged rows [n, C]
+    const int32_t* tlbr;      // [n, 5]
+    int32_t* idx;             // [n] merged_token_1d_idx
+    int pad_in, pad_out;      // left pad of the input row / of the output row (Lout - L'_b)
+    int start, n, length;     // system tokens, merged rows, video tokens
+    int hw, w;                // H * W and W of the video grid
+};
+struct PackArgs {
+    const char* hidden;       // [B, L, C] layer output
+    char* out;                // [B, Lout, C]
+    int64_t* mask;            // [B, Lout]
+    const int64_t* pos_in;    // see STTM_PACK_POS_*
+    int64_t* pos_out;
+    int64_t hid_stride_b, hid_stride_t;   // bytes
+    int64_t pos_stride_a, pos_stride_b;   // elements
+    int B, Lout, row_bytes, packs, pos_mode, b0;   // b0: batch row of rows[0]
+    PackRow rows[kBatchMax];
+};
+hipError_t launch_pack_merged(const PackArgs& a, int n_rows, int pack_bytes, hipStream_t stream);
 constexpr int kOctMaxLevels = 8;
 
 struct OctArgs {

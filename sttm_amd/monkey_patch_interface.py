@@ -12,11 +12,13 @@ build targets the transformers that is installed (5.x decoder-layer API): the pa
 installed `Qwen2Model.forward` with the merge step inserted before layer `sa_start_layer_idx` on prefill.
 State read by the hook is the same: `self.image_token_start_index`, `self.image_token_length`, `self.num_frame`
 (0-d tensors set by generate(), llava/model/language_model/llava_qwen.py:141-143), plus `image_H/image_W` for Qwen2-VL.
+For "quadtree" they may also be 1-D tensors of length B: the batched hook of a left-padded batch ("Batched prompts").
 """
 import torch
 
 from . import patch_hooks
-from .quadtree_interface import get_quadtree_features, get_quadtree_features_into
+from .quadtree_interface import (get_quadtree_features, get_quadtree_features_batch_reused, get_quadtree_features_into,
+                                 pack_merged_batch)
 from .tome_interface import get_tome_features
 
 _UNIMPLEMENTED = {
@@ -49,9 +51,109 @@ def _rebuild_masks(self, mask_map, hidden_states, past_key_values, position_ids=
     return out
 
 
+# ---- batched prompts ("quadtree" on B > 1 left-padded rows) ---------------------------------------------------------------
+_QWEN2_ROW_ATTRS = ("image_token_start_index", "image_token_length", "num_frame")
+_QWEN2VL_ROW_ATTRS = _QWEN2_ROW_ATTRS + ("image_H", "image_W")
+
+
+def _per_row(v, B, name):
+    """A hook attribute as B ints: a 0-d tensor or an int is the same for every row, a 1-D tensor has one entry per row."""
+    if torch.is_tensor(v) and v.dim() == 1:
+        if v.numel() != B:
+            raise ValueError(f"{name} has {v.numel()} entries for a batch of {B} prompts")
+        return [int(x) for x in v.tolist()]
+    return [_item(v)] * B
+
+
+def _batched_rows(self, inputs_embeds, attention_mask, prefilling, names):
+    """None (the batch-1 hook) or (pads, per-row attribute lists) when the batched quadtree hook runs on this prefill: B > 1 or an
+    attribute is 1-D.  Pad counts come from the 2-D attention mask, read once before any layer is enqueued."""
+    if not prefilling or self.sttm_pattern != "quadtree" or getattr(self, "image_token_length", None) is None:
+        return None
+    B, L = inputs_embeds.shape[:2]
+    if B == 1 and not any(torch.is_tensor(getattr(self, n, None)) and getattr(self, n).dim() == 1 for n in names):
+        return None
+    attrs = [_per_row(getattr(self, n), B, n) for n in names]
+    if attention_mask is None:
+        return [0] * B, attrs
+    if not torch.is_tensor(attention_mask) or attention_mask.dim() != 2 or tuple(attention_mask.shape) != (B, L):
+        raise ValueError("the batched quadtree hook needs the 2-D [B, L] attention mask of the prompts")
+    m = attention_mask.to(torch.bool)
+    valid, first = torch.stack([m.sum(-1), m.to(torch.int32).argmax(-1)]).tolist()
+    pads = [L - v for v in valid]
+    if any(v == 0 or f != p for v, f, p in zip(valid, first, pads)):
+        raise ValueError("the batched quadtree hook needs LEFT-padded prompts (generate reads the last column)")
+    return pads, attrs
+
+
+def _positions_from_mask(attention_mask, inputs_embeds):
+    """What generate passes for a left-padded batch: every row counts from its first valid token, pads get 1."""
+    B, L = inputs_embeds.shape[:2]
+    if attention_mask is None:
+        return torch.arange(L, device=inputs_embeds.device).unsqueeze(0).expand(B, -1)
+    m = attention_mask.to(device=inputs_embeds.device, dtype=torch.long)
+    return (m.cumsum(-1) - 1).masked_fill(m == 0, 1)
+
+
+def _merged_layout_masks(self, mask_map, hidden_states, mask2d, past_key_values):
+    """Masks of the layers from sa_start_layer_idx on, over the merged layout's 2-D key mask.  Prefill (past_key_values None): the
+    keys are the merged block itself.  Decode: sized against the first such layer of each type in the cache (the earlier layers
+    hold the long layout)."""
+    from transformers.masking_utils import create_causal_mask, create_sliding_window_causal_mask
+    types = self.config.layer_types
+    out = {}
+    for k in mask_map:
+        kw = dict(config=self.config, inputs_embeds=hidden_states, attention_mask=mask2d, past_key_values=past_key_values,
+                  position_ids=None)
+        if past_key_values is not None:
+            first = next((i for i in range(self.sa_start_layer_idx, len(types)) if types[i] == k), None)
+            if first is None:
+                out[k] = mask_map[k]
+                continue
+            kw["layer_idx"] = first
+        out[k] = create_sliding_window_causal_mask(**kw) if k == "sliding_attention" else create_causal_mask(**kw)
+    return out
+
+
+def _decode_masks(self, mask_map, inputs_embeds, attention_mask, past_key_values):
+    """Decode step after a batched merge: the merged layout's prefill key mask (kept with the cache) extended by the columns generate
+    appended after the prompt, one valid column per generated token.  None when the cache holds no batched merge."""
+    state = getattr(past_key_values, "sttm_merged_mask", None) if past_key_values is not None else None
+    if state is None:
+        return None
+    m0, L0 = state
+    total = past_key_values.get_seq_length(self.sa_start_layer_idx) + inputs_embeds.shape[1]
+    extra = total - m0.shape[1]
+    if torch.is_tensor(attention_mask) and attention_mask.dim() == 2 and attention_mask.shape[1] == L0 + extra:
+        tail = attention_mask[:, L0:].to(device=m0.device, dtype=m0.dtype)
+    else:
+        tail = m0.new_ones((m0.shape[0], extra))
+    return _merged_layout_masks(self, mask_map, inputs_embeds, torch.cat([m0, tail], dim=1), past_key_values)
+
+
+def _truncate_rows(ids, pads, mask2d, L):
+    """[B or 1, L] ids -> [B, L'max]: row b's valid columns keep its first L'_b ids (the batch-1 truncation), pads get 1."""
+    B, Lout = mask2d.shape
+    ids = ids.expand(B, L)
+    shift = torch.tensor([Lout - int(v) - p for v, p in zip(mask2d.sum(-1).tolist(), pads)], device=ids.device)
+    col = (torch.arange(Lout, device=ids.device)[None] - shift[:, None]).clamp(0, L - 1)
+    return torch.where(mask2d.to(torch.bool), ids.gather(1, col), torch.ones_like(col))
+
+
+def _keep_merged_mask(past_key_values, mask2d, L):
+    if past_key_values is not None:
+        past_key_values.sttm_merged_mask = (mask2d, L)
+
+
+def _reset_merged_mask(past_key_values):
+    if past_key_values is not None and getattr(past_key_values, "sttm_merged_mask", None) is not None:
+        past_key_values.sttm_merged_mask = None
+
+
 def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                               inputs_embeds=None, use_cache=None, **kwargs):
-    """transformers 5.x Qwen2Model.forward + the STTM / ToMe hook (prefill, batch 1)."""
+    """transformers 5.x Qwen2Model.forward + the STTM / ToMe hook (prefill).  "quadtree" on B > 1 left-padded prompts (or 1-D hook
+    attributes) takes the batched hook; every other case runs the batch-1 hook."""
     from transformers.cache_utils import DynamicCache
     from transformers.masking_utils import create_causal_mask, create_sliding_window_causal_mask
     from transformers.modeling_outputs import BaseModelOutputWithPast
@@ -62,6 +164,11 @@ def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, positio
     if use_cache and past_key_values is None:
         past_key_values = DynamicCache(config=self.config)
     prefilling = _is_prefill(past_key_values)
+    rows = _batched_rows(self, inputs_embeds, attention_mask, prefilling, _QWEN2_ROW_ATTRS)
+    if prefilling:
+        _reset_merged_mask(past_key_values)
+    if position_ids is None and rows is not None:
+        position_ids = _positions_from_mask(attention_mask, inputs_embeds)
     if position_ids is None:
         seen = past_key_values.get_seq_length() if past_key_values is not None else 0
         position_ids = (torch.arange(inputs_embeds.shape[1], device=inputs_embeds.device) + seen).unsqueeze(0)
@@ -71,11 +178,28 @@ def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, positio
         mask_map = {"full_attention": create_causal_mask(**mk)}
         if getattr(self, "has_sliding_layers", False):
             mask_map["sliding_attention"] = create_sliding_window_causal_mask(**mk)
+    # decode after a batched merge: the layers from the merge layer on read the merged layout
+    late_masks = None if prefilling else _decode_masks(self, mask_map, inputs_embeds, attention_mask, past_key_values)
     hidden_states = inputs_embeds
     position_embeddings = self.rotary_emb(hidden_states, position_ids)
     merged = False
     for i, layer in enumerate(self.layers[: self.config.num_hidden_layers]):
-        if (prefilling and self.sttm_pattern == "pyrd" and i in self.sa_pyrd_llm_idxs
+        if late_masks is not None and i == self.sa_start_layer_idx:
+            mask_map = late_masks
+        if rows is not None and not merged and i == self.sa_start_layer_idx:
+            pads, (starts, lengths, Ts) = rows
+            head_dim = layer.self_attn.head_dim if self.sim_per_head else None
+            L = hidden_states.size(1)
+            hidden_states, mask2d, position_ids, idx = patch_hooks.quadtree_merge_llava_batched(
+                hidden_states, position_ids, pads, starts, lengths, Ts, type(self).sttm_merge_batch_fn, type(self).sttm_pack_fn,
+                self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
+                slow_ver=self.sttm_slow_ver, head_dim=head_dim)
+            self.merged_token_1d_idx = idx
+            position_embeddings = self.rotary_emb(hidden_states, position_ids)
+            mask_map = _merged_layout_masks(self, mask_map, hidden_states, mask2d, None)
+            _keep_merged_mask(past_key_values, mask2d, L)
+            merged = True
+        elif (prefilling and self.sttm_pattern == "pyrd" and i in self.sa_pyrd_llm_idxs
                 and getattr(self, "image_token_length", None) is not None):
             # fixed-size pyramid baseline: may fire at several layers, each shrinking the frames further
             start, length, T = _item(self.image_token_start_index), _item(self.image_token_length), _item(self.num_frame)
@@ -139,6 +263,11 @@ def _qwen2vl_forward_with_merge(self, input_ids=None, attention_mask=None, posit
     if inputs_embeds is None:
         inputs_embeds = self.embed_tokens(input_ids)
     prefilling = _is_prefill(past_key_values)
+    rows = _batched_rows(self, inputs_embeds, attention_mask, prefilling, _QWEN2VL_ROW_ATTRS)
+    if prefilling:
+        _reset_merged_mask(past_key_values)
+    if position_ids is None and rows is not None:
+        position_ids = _positions_from_mask(attention_mask, inputs_embeds)[None].expand(3, -1, -1)
     if position_ids is None:
         seen = past_key_values.get_seq_length() if past_key_values is not None else 0
         position_ids = torch.arange(inputs_embeds.shape[1], device=inputs_embeds.device) + seen
@@ -155,11 +284,28 @@ def _qwen2vl_forward_with_merge(self, input_ids=None, attention_mask=None, posit
         mask_map = {"full_attention": create_causal_mask(**mk)}
         if getattr(self, "has_sliding_layers", False):
             mask_map["sliding_attention"] = create_sliding_window_causal_mask(**mk)
+    late_masks = None if prefilling else _decode_masks(self, mask_map, inputs_embeds, attention_mask, past_key_values)
     hidden_states = inputs_embeds
     position_embeddings = self.rotary_emb(hidden_states, position_ids)
     merged = False
     for i, layer in enumerate(self.layers):
-        if prefilling and not merged and i == self.sa_start_layer_idx and getattr(self, "image_token_length", None) is not None:
+        if late_masks is not None and i == self.sa_start_layer_idx:
+            mask_map = late_masks
+        if rows is not None and not merged and i == self.sa_start_layer_idx:
+            pads, (starts, lengths, Ts, Hs, Ws) = rows
+            L = hidden_states.size(1)
+            hidden_states, mask2d, position_ids, idx = patch_hooks.quadtree_merge_qwen2vl_batched(
+                hidden_states, position_ids, pads, starts, lengths, Ts, Hs, Ws, type(self).sttm_merge_batch_fn, type(self).sttm_pack_fn,
+                self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
+                slow_ver=self.sttm_slow_ver)
+            if text_position_ids is not None:
+                text_position_ids = _truncate_rows(text_position_ids, pads, mask2d, L)
+            self.merged_token_1d_idx = idx
+            position_embeddings = self.rotary_emb(hidden_states, position_ids)
+            mask_map = _merged_layout_masks(self, mask_map, hidden_states, mask2d, None)
+            _keep_merged_mask(past_key_values, mask2d, L)
+            merged = True
+        elif prefilling and not merged and i == self.sa_start_layer_idx and getattr(self, "image_token_length", None) is not None:
             start, length, T = _item(self.image_token_start_index), _item(self.image_token_length), _item(self.num_frame)
             H, W = _item(self.image_H), _item(self.image_W)
             if self.sttm_pattern == "quadtree":
@@ -207,6 +353,15 @@ def _fused_merge_fn(cls):
     return get_quadtree_features_into if cls.sttm_merge_fn is get_quadtree_features else None
 
 
+def _install_batched_fns(cls):
+    """Injection points of the batched hook, next to `sttm_merge_fn`: the merge of the B videos and the ragged pack (tests put the
+    CPU oracle and a torch restatement here)."""
+    if not hasattr(cls, "sttm_merge_batch_fn"):
+        cls.sttm_merge_batch_fn = staticmethod(get_quadtree_features_batch_reused)
+    if not hasattr(cls, "sttm_pack_fn"):
+        cls.sttm_pack_fn = staticmethod(pack_merged_batch)
+
+
 def replace_qwen2_with_quadtree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90, sa_tree_temporal_thresh=-1.0,
                                      sa_tree_root_level=0, sa_tree_weighted_avg=False, sttm_slow_ver=False,
                                      sim_per_head=False, **kwargs):
@@ -222,6 +377,7 @@ def replace_qwen2_with_quadtree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90, 
     cls.sim_per_head = sim_per_head
     if not hasattr(cls, "sttm_merge_fn"):
         cls.sttm_merge_fn = staticmethod(get_quadtree_features)
+    _install_batched_fns(cls)
     if not hasattr(cls, "_sttm_original_forward"):
         cls._sttm_original_forward = cls.forward
     cls.forward = _qwen2_forward_with_merge
@@ -328,6 +484,7 @@ def replace_qwen2vl_with_quadtree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90
     cls.sttm_slow_ver = sttm_slow_ver
     if not hasattr(cls, "sttm_merge_fn"):
         cls.sttm_merge_fn = staticmethod(get_quadtree_features)
+    _install_batched_fns(cls)
     if not hasattr(cls, "_sttm_original_forward"):
         cls._sttm_original_forward = cls.forward
     cls.forward = _qwen2vl_forward_with_merge

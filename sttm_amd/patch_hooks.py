@@ -75,6 +75,48 @@ def quadtree_merge_qwen2vl(hidden_states, position_ids, start, length, T, H, W, 
     return merged, pos, cache_position, idx
 
 
+# ---- batched prompts (B >= 1 left-padded rows, one video per row) ------------------------------------------------------------
+# Row b's indices count from its first valid token, pads[b] columns in: the same numbers a batch-1 call of that row would use.
+# merge_batch_fn(videos, threshold, temporal_thresh, root_level, weighted_avg, slow_ver=, head_dim=) -> B (features, num_patches, tlbr)
+# (sttm_amd.quadtree_interface.get_quadtree_features_batch_reused on the device); pack_fn(hidden_states, merged, geom, Lout, position_ids,
+# pos_mode) -> (hidden [B, Lout, C], key mask [B, Lout], position ids, B merged_token_1d_idx) (quadtree_interface.pack_merged_batch).
+POS_TRUNCATE, POS_GATHER3 = 1, 2         # STTM_PACK_POS_* of include/sttm_hip.h
+
+
+def _merge_and_pack(hidden_states, position_ids, rows, merge_batch_fn, pack_fn, merge_args, merge_kwargs, pos_mode):
+    """rows: B tuples (pad, start, length, T, H, W).  One batched merge of the B videos, then one pack into the compact block
+    [B, L'max, C] with L'_b = L - pad_b - length_b + N'_b (N'_b is known on the host once the merge returns)."""
+    L = hidden_states.size(1)
+    videos = [_video_view(hidden_states[b, p + s:p + s + n], T, H, W) for b, (p, s, n, T, H, W) in enumerate(rows)]
+    res = merge_batch_fn(videos, *merge_args, **merge_kwargs)
+    geom = [(p, s, n, int(feat.size(0)), T, H, W) for (p, s, n, T, H, W), (feat, _, _) in zip(rows, res)]
+    Lout = max(L - p - n + m for p, _, n, m, _, _, _ in geom)
+    return pack_fn(hidden_states, [(feat, tlbr) for feat, _, tlbr in res], geom, Lout, position_ids, pos_mode)
+
+
+def quadtree_merge_llava_batched(hidden_states, position_ids, pads, starts, lengths, Ts, merge_batch_fn, pack_fn, threshold,
+                                 temporal_thresh, root_level, weighted_avg, slow_ver=False, head_dim=None):
+    """quadtree_merge_llava on every row of a left-padded batch [B, L, C]; position_ids [B or 1, L] are TRUNCATED per row (:114).
+    Returns (hidden_states [B, L'max, C], key mask [B, L'max] int64, position_ids [B, L'max], list of B merged_token_1d_idx)."""
+    rows = []
+    for p, s, n, T in zip(pads, starts, lengths, Ts):
+        H = int(math.sqrt(n // T))                                        # :97
+        rows.append((p, s, n, T, H, H))
+    return _merge_and_pack(hidden_states, position_ids, rows, merge_batch_fn, pack_fn,
+                           (threshold, temporal_thresh, root_level, weighted_avg), dict(slow_ver=slow_ver, head_dim=head_dim),
+                           POS_TRUNCATE)
+
+
+def quadtree_merge_qwen2vl_batched(hidden_states, position_ids, pads, starts, lengths, Ts, Hs, Ws, merge_batch_fn, pack_fn, threshold,
+                                   temporal_thresh, root_level, weighted_avg, slow_ver=False):
+    """quadtree_merge_qwen2vl on every row of a left-padded batch: the 3-D mRoPE ids [3, B or 1, L] of every row are GATHERED by its
+    merged index, system / instruction ids kept (:109-113).  Returns (hidden_states [B, L'max, C], key mask [B, L'max] int64,
+    position_ids [3, B, L'max], list of B merged_token_1d_idx)."""
+    rows = list(zip(pads, starts, lengths, Ts, Hs, Ws))
+    return _merge_and_pack(hidden_states, position_ids, rows, merge_batch_fn, pack_fn,
+                           (threshold, temporal_thresh, root_level, weighted_avg), dict(slow_ver=slow_ver), POS_GATHER3)
+
+
 def tome_merge(hidden_states, position_ids, start, length, T, merge_fn, prune_ratio, tome_ver, H=None, W=None,
                gather_positions=False):
     """ToMe hook.  LLaVA (token_merging_monkey_patch/tome_attn_monkey_patch.py:88-107): H = W = sqrt(len / T), position_ids

@@ -436,7 +436,8 @@ def get_quadtree_features_batch(videos, threshold, temporal_thresh=-1.0, root_le
     Memory: N' is known only after the kernels ran, so every video gets worst-case output rows ([T*H*W, C] ...); without `out` a call
     allocates them (96 headline videos: 10 GB for 4.4 GB of results, alive as long as the returned views).  `out = (features [n, T*H*W, C],
     num_patches [n, T*H*W] int32, tlbr [n, T*H*W, 5] int32)` -- CALLER-OWNED blocks for n >= len(videos) videos of ONE shape / dtype,
-    reused call after call -- makes the call allocation-free; the results are leading views into them."""
+    reused call after call -- makes the call allocation-free; the results are leading views into them.  For videos of several shapes
+    `out` may be a callable `out((T, C, H, W), dtype, n)` that returns such blocks for each shape group (see BatchOutBlocks)."""
     if not videos:
         return []
     dev = videos[0].device
@@ -455,6 +456,108 @@ def get_quadtree_features_batch(videos, threshold, temporal_thresh=-1.0, root_le
 def release_streams():
     """Destroy the internal streams / events the batch entry point created for the calling host thread (C ABI: sttm_release_streams)."""
     return _lib.load().sttm_release_streams()
+
+
+class BatchOutBlocks:
+    """Caller-owned `out=` blocks of get_quadtree_features_batch for videos of MIXED shapes: one worst-case block set per
+    (shape, dtype), grown to the largest group seen and kept across calls (at most `limit` shapes, oldest dropped first), so a
+    shape group that comes back does not allocate.  The results of a call are views into the blocks: they are overwritten by the
+    next call that uses the same blocks (stream-ordered on one stream)."""
+
+    def __init__(self, device, limit=8):
+        self.device = device
+        self.blocks = _lib.BoundedCache(limit)
+
+    def __call__(self, shape, dtype, n):
+        T, C, H, W = shape
+        N = T * H * W
+        key = (tuple(shape), dtype)
+        blk = self.blocks.get(key)
+        if blk is None or blk[0].shape[0] < n:
+            blk = (torch.empty((n, N, C), dtype=dtype, device=self.device), torch.empty((n, N), dtype=torch.int32, device=self.device),
+                   torch.empty((n, N, 5), dtype=torch.int32, device=self.device))
+        self.blocks[key] = blk
+        return blk
+
+
+_hook_blocks = _lib.BoundedCache(8)
+
+
+def get_quadtree_features_batch_reused(videos, threshold, temporal_thresh=-1.0, root_level=0, weighted_avg=False, slow_ver=False,
+                                       head_dim=None):
+    """get_quadtree_features_batch into BatchOutBlocks owned by the library, one set per (device, current stream): the merge step of
+    the batched decoder hook.  The returned (features, num_patches, tlbr) views are valid until the next call on the same stream."""
+    if not videos:
+        return []
+    dev = videos[0].device
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream) if videos[0].is_cuda else None
+    blocks = _hook_blocks.get(key)
+    if blocks is None:
+        blocks = BatchOutBlocks(dev)
+    _hook_blocks[key] = blocks
+    return get_quadtree_features_batch(videos, threshold, temporal_thresh, root_level, weighted_avg, slow_ver=slow_ver,
+                                       head_dim=head_dim, out=blocks)
+
+
+def pack_merged_batch(hidden_states, merged, geom, Lout, position_ids=None, pos_mode=_lib.PACK_POS_NONE):
+    """The ragged pack of the batched hook (sttm_pack_merged_batch, one launch per 16 rows on the current stream, no sync).
+      hidden_states [B, L, C] left-padded layer output; merged: B pairs (features [>= N'_b, C], tlbr [>= N'_b, 5] int32);
+      geom: B tuples (pad, start, length, N'_b, T, H, W); Lout >= every L - pad - length + N'_b.
+      position_ids: pos_mode PACK_POS_TRUNCATE [B or 1, L], PACK_POS_GATHER3 [3, B or 1, L] (int64).
+    Returns (hidden [B, Lout, C] left-padded with zero rows, key mask [B, Lout] int64, position ids or None, list of B int32
+    merged_token_1d_idx)."""
+    if not hidden_states.is_cuda:
+        raise RuntimeError("sttm_amd runs on the GPU only: the hidden states must be a CUDA (ROCm) tensor; there is no CPU fallback")
+    dtype = _DTYPE_CODE.get(hidden_states.dtype)
+    if dtype is None:
+        raise NotImplementedError(f"dtype {hidden_states.dtype} is not supported (float32, bfloat16, float16)")
+    B, L, C = hidden_states.shape
+    if len(merged) != B or len(geom) != B:
+        raise ValueError(f"pack: {len(merged)} merged videos and {len(geom)} geometry rows for a batch of {B}")
+    dev = hidden_states.device
+    if hidden_states.stride(-1) != 1:
+        hidden_states = hidden_states.contiguous()
+    feats, tlbrs = [], []
+    for f, t in merged:
+        if (f.dtype != hidden_states.dtype or f.device != dev or f.dim() != 2 or f.size(1) != C or not f.is_contiguous()
+                or t.dtype != torch.int32 or t.device != dev or t.dim() != 2 or t.size(1) != 5 or not t.is_contiguous()):
+            raise ValueError(f"pack: merged rows must be contiguous [n, {C}] {hidden_states.dtype} with tlbr [n, 5] int32 on {dev}")
+        feats.append(f)
+        tlbrs.append(t)
+    for (f, t), g in zip(merged, geom):
+        if f.size(0) < g[3] or t.size(0) < g[3]:
+            raise ValueError(f"pack: a video has {f.size(0)} merged rows, its geometry says {g[3]}")
+    out = torch.empty((B, Lout, C), dtype=hidden_states.dtype, device=dev)
+    mask = torch.empty((B, Lout), dtype=torch.int64, device=dev)
+    idx = torch.empty(max(1, sum(int(g[3]) for g in geom)), dtype=torch.int32, device=dev)
+    idx_list = list(torch.split(idx[:sum(int(g[3]) for g in geom)], [int(g[3]) for g in geom]))
+    pos_out, pos_in, sa, sb = None, None, 0, 0
+    if pos_mode == _lib.PACK_POS_TRUNCATE:
+        pos_in = position_ids.to(device=dev, dtype=torch.int64)
+        if pos_in.dim() != 2 or pos_in.size(0) not in (1, B) or pos_in.size(1) != L:
+            raise ValueError(f"pack: position ids of shape {tuple(pos_in.shape)} for [{B}, {L}]")
+        pos_in = pos_in if pos_in.stride(-1) == 1 else pos_in.contiguous()
+        sb = pos_in.stride(0) if pos_in.size(0) == B else 0
+        pos_out = torch.empty((B, Lout), dtype=torch.int64, device=dev)
+    elif pos_mode == _lib.PACK_POS_GATHER3:
+        pos_in = position_ids.to(device=dev, dtype=torch.int64)
+        if pos_in.dim() != 3 or pos_in.size(0) != 3 or pos_in.size(1) not in (1, B) or pos_in.size(2) != L:
+            raise ValueError(f"pack: 3-D position ids of shape {tuple(pos_in.shape)} for [3, {B}, {L}]")
+        pos_in = pos_in if pos_in.stride(-1) == 1 else pos_in.contiguous()
+        sa = pos_in.stride(0)
+        sb = pos_in.stride(1) if pos_in.size(1) == B else 0
+        pos_out = torch.empty((3, B, Lout), dtype=torch.int64, device=dev)
+    vp = ctypes.c_void_p * B
+    flat = [int(v) for g in geom for v in g]
+    with torch.cuda.device(dev):
+        rc = _lib.load().sttm_pack_merged_batch(
+            B, C, dtype, hidden_states.data_ptr(), hidden_states.stride(0), hidden_states.stride(1), L,
+            vp(*[f.data_ptr() for f in feats]), vp(*[t.data_ptr() for t in tlbrs]), (ctypes.c_int32 * len(flat))(*flat), int(Lout),
+            out.data_ptr(), mask.data_ptr(), vp(*[i.data_ptr() for i in idx_list]),
+            int(pos_mode), pos_in.data_ptr() if pos_in is not None else None, sa, sb,
+            pos_out.data_ptr() if pos_out is not None else None, torch.cuda.current_stream(dev).cuda_stream)
+    _lib.raise_for(rc)
+    return out, mask, pos_out, idx_list
 
 
 def _batch_locked(st, videos, dev, threshold, temporal_thresh, root_level, weighted_avg, slow_ver, head_dim, events, flags, dest=None):
@@ -489,9 +592,12 @@ def _batch_locked(st, videos, dev, threshold, temporal_thresh, root_level, weigh
         # the outputs of a group in THREE allocations (worst-case rows per video, returned as leading views like the one-video call):
         # one torch.empty per tensor and video kept the host busy for ~7 us per video between two calls, with the device idle
         if dest is not None:
-            if len(groups) != 1:
+            if callable(dest):
+                feats, npatches, tlbrs = dest(shape, dt, n)
+            elif len(groups) != 1:
                 raise ValueError("out= takes videos of ONE shape / dtype / stride set")
-            feats, npatches, tlbrs = dest
+            else:
+                feats, npatches, tlbrs = dest
             ok = (feats.is_cuda and feats.device == dev and feats.dtype == dt and feats.is_contiguous() and tuple(feats.shape[1:]) == (N, C)
                   and feats.shape[0] >= n and npatches.dtype == torch.int32 and npatches.is_contiguous() and tuple(npatches.shape) == (feats.shape[0], N)
                   and npatches.device == dev and tlbrs.dtype == torch.int32 and tlbrs.is_contiguous() and tlbrs.device == dev
