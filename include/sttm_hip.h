@@ -380,6 +380,33 @@ int sttm_dycoke_ttm(const void* x, int T, int P, int C, int dtype, int k, void* 
                     void* out, int64_t* out_idx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DyCoke stage 2, the decode-time half of the "dycoke" pattern (token_merging_monkey_patch/dycoke_attn_monkey_patch.py), batch 1,
+ * one query token.  float32, bfloat16, float16; head dimensions 64 and 128; Hq a multiple of Hkv (query head h reads KV head
+ * h / (Hq / Hkv)), Hq <= 256, Lk <= 2^24.  q [Hq, D] and the cache layer K / V [Hkv, Lk, D] are addressed by strides in ELEMENTS (the
+ * channel stride is 1); pointers and strides must keep every row on a 16-byte boundary.  All three calls enqueue on `stream`, never
+ * synchronise with the host and keep nothing between calls.
+ *
+ * sttm_decode_attn_scores   replaces the eager run of layer dycoke_l - 1 and `attn[1].mean(1)[0, -1]` (:80, :410-411):
+ *   score [Lk] float32 = mean over the query heads of softmax(scale * q K^T).  Kept in float32 (the reference rounds the probabilities
+ *   to the model dtype before the mean).
+ * sttm_decode_select_keep   replaces update_cache (:62-77, the top-k and the .tolist()):
+ *   window = [start, min(start + n0, Lk)); keep [n_keep] int32 on the device = [0, start) ++ the num_keep largest scores of the window,
+ *   ASCENDING BY INDEX, ties to the smaller index ++ [start + n0, Lk); n_keep = start + num_keep + max(Lk - start - n0, 0) must be
+ *   passed.  num_keep above the window length is STTM_ERR_ARG (the reference's topk raises).  One workgroup; any window length.
+ * sttm_decode_attn_gathered replaces the two torch.gather of the whole cache and the attention over the copies (:54-60):
+ *   out [Hq, D] contiguous, model dtype = softmax(scale * q K[keep]^T) V[keep], float32 accumulation, rows read in place.  Entries of
+ *   keep outside [0, Lk) are ignored.
+ * workspace >= sttm_decode_workspace_bytes(Hq, Lk, n_keep) serves all three (0 and sttm_last_error() for a refused shape).
+ * ------------------------------------------------------------------------------------------------ */
+size_t sttm_decode_workspace_bytes(int Hq, int Lk, int n_keep);
+int sttm_decode_attn_scores(const void* q, int64_t q_stride_h, const void* k, int64_t k_stride_h, int64_t k_stride_l, int Hq, int Hkv, int Lk,
+                            int D, int dtype, float scale, void* workspace, size_t workspace_bytes, float* score, void* stream);
+int sttm_decode_select_keep(const float* score, int Lk, int start, int n0, int num_keep, int32_t* keep, int n_keep, void* stream);
+int sttm_decode_attn_gathered(const void* q, int64_t q_stride_h, const void* k, int64_t k_stride_h, int64_t k_stride_l, const void* v,
+                              int64_t v_stride_h, int64_t v_stride_l, int Hq, int Hkv, int Lk, int D, int dtype, float scale, const int32_t* keep,
+                              int n_keep, void* workspace, size_t workspace_bytes, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Octree baseline over the whole cubes of a clip: replaces octree_build (token_merging_utils/octree_utils.py:293-373).
  *   x        [n_cubes * side, side, side, C] dense channels-last tokens (a cube = `side` consecutive frames of side x side)
  *   feat_out [n_cubes * side^3, C] worst case; rows [0, N') are valid, ordered by the first-corner leaf index (:369-373)

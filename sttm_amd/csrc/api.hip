@@ -1128,6 +1128,80 @@ int sttm_dycoke_ttm(const void* x, int T, int P, int C, int dtype, int k, void* 
     return STTM_OK;
 }
 
+// ---- DyCoke stage 2 (decode) -------------------------------------------------------------------------------------------------
+static const int kDecodeMaxHq = 256, kDecodeMaxLk = 1 << 24;
+static inline size_t align256(size_t b) { return (b + 255) / 256 * 256; }
+// [logits Hq * Lk | tile statistics | partial rows of the gathered attention]; the tile counts are those of the smallest tile (32 rows)
+static inline size_t decode_stat_bytes(int Hq, int rows) { return align256((size_t)((rows + 31) / 32) * Hq * 2 * 4); }
+static inline size_t decode_logit_bytes(int Hq, int Lk) { return align256((size_t)Hq * Lk * 4); }
+
+size_t sttm_decode_workspace_bytes(int Hq, int Lk, int n_keep) {
+    if (Hq < 1 || Lk < 1 || n_keep < 0) { fail(STTM_ERR_ARG, "bad Hq/Lk/n_keep"); return 0; }
+    if (Hq > kDecodeMaxHq) { fail(STTM_ERR_UNSUPPORTED, "more than %d query heads", kDecodeMaxHq); return 0; }
+    if (Lk > kDecodeMaxLk || n_keep > Lk) { fail(STTM_ERR_UNSUPPORTED, "more than 2^24 keys, or more kept rows than keys"); return 0; }
+    const int rows = n_keep > Lk ? n_keep : Lk;
+    return decode_logit_bytes(Hq, Lk) + decode_stat_bytes(Hq, rows) + align256((size_t)((n_keep + 31) / 32) * Hq * 128 * 4) + 256;
+}
+
+static int decode_check(const char* what, const void* q, int64_t q_sh, const void* k, int64_t k_sh, int64_t k_sl, int Hq, int Hkv, int Lk,
+                        int D, int dtype) {
+    if (!q || !k || Hq < 1 || Hkv < 1 || Lk < 1 || Hq % Hkv) return fail(STTM_ERR_ARG, "%s: bad pointer or shape", what);
+    if (dtype < 0 || dtype > 2) return fail(STTM_ERR_ARG, "%s: bad dtype", what);
+    if (D != 64 && D != 128) return fail(STTM_ERR_UNSUPPORTED, "%s: head dimension %d (64 and 128 are built)", what, D);
+    if (Hq > kDecodeMaxHq) return fail(STTM_ERR_UNSUPPORTED, "%s: more than %d query heads", what, kDecodeMaxHq);
+    if (Lk > kDecodeMaxLk) return fail(STTM_ERR_UNSUPPORTED, "%s: more than 2^24 keys", what);
+    const int64_t eb = elem_bytes(dtype);
+    if (q_sh < 0 || k_sh < 0 || k_sl < 0) return fail(STTM_ERR_UNSUPPORTED, "%s: negative strides are not supported", what);
+    if (reinterpret_cast<uintptr_t>(q) % 16 || reinterpret_cast<uintptr_t>(k) % 16 || (q_sh * eb) % 16 || (k_sh * eb) % 16 || (k_sl * eb) % 16)
+        return fail(STTM_ERR_UNSUPPORTED, "%s: rows must start on 16-byte boundaries (pointer and strides)", what);
+    return STTM_OK;
+}
+
+int sttm_decode_attn_scores(const void* q, int64_t q_stride_h, const void* k, int64_t k_stride_h, int64_t k_stride_l, int Hq, int Hkv, int Lk,
+                            int D, int dtype, float scale, void* workspace, size_t workspace_bytes, float* score, void* stream_) {
+    const int rc = decode_check("decode scores", q, q_stride_h, k, k_stride_h, k_stride_l, Hq, Hkv, Lk, D, dtype);
+    if (rc != STTM_OK) return rc;
+    if (!workspace || !score) return fail(STTM_ERR_ARG, "decode scores: bad pointer");
+    if (workspace_bytes < decode_logit_bytes(Hq, Lk) + decode_stat_bytes(Hq, Lk)) return fail(STTM_ERR_ARG, "workspace too small");
+    char* ws = reinterpret_cast<char*>(workspace);
+    hipError_t e = sttm::launch_decode_scores(q, q_stride_h, k, k_stride_h, k_stride_l, Hq, Hkv, Lk, D, dtype, scale,
+                                              reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + decode_logit_bytes(Hq, Lk)), score,
+                                              reinterpret_cast<hipStream_t>(stream_));
+    if (e != hipSuccess) return fail(STTM_ERR_LAUNCH, "decode score kernels: %s", hipGetErrorString(e));
+    return STTM_OK;
+}
+
+int sttm_decode_select_keep(const float* score, int Lk, int start, int n0, int num_keep, int32_t* keep, int n_keep, void* stream_) {
+    if (!score || !keep || Lk < 1 || start < 0 || n0 < 0 || num_keep < 0 || start > Lk) return fail(STTM_ERR_ARG, "decode select: bad pointer or shape");
+    if (Lk > kDecodeMaxLk) return fail(STTM_ERR_UNSUPPORTED, "decode select: more than 2^24 keys");
+    const int64_t end = (int64_t)start + n0 < Lk ? (int64_t)start + n0 : Lk;
+    const int window = (int)(end - start);
+    if (num_keep > window) return fail(STTM_ERR_ARG, "selected index k out of range (num_keep %d of a window of %d scores)", num_keep, window);
+    const int tail_len = (int64_t)start + n0 < Lk ? (int)(Lk - start - n0) : 0;
+    if (n_keep != start + num_keep + tail_len) return fail(STTM_ERR_ARG, "decode select: n_keep must be start + num_keep + tail (%d)", start + num_keep + tail_len);
+    hipError_t e = sttm::launch_decode_select(score, start, window, num_keep, start + n0, tail_len, keep, reinterpret_cast<hipStream_t>(stream_));
+    if (e != hipSuccess) return fail(STTM_ERR_LAUNCH, "decode select kernel: %s", hipGetErrorString(e));
+    return STTM_OK;
+}
+
+int sttm_decode_attn_gathered(const void* q, int64_t q_stride_h, const void* k, int64_t k_stride_h, int64_t k_stride_l, const void* v,
+                              int64_t v_stride_h, int64_t v_stride_l, int Hq, int Hkv, int Lk, int D, int dtype, float scale, const int32_t* keep,
+                              int n_keep, void* workspace, size_t workspace_bytes, void* out, void* stream_) {
+    int rc = decode_check("gathered attention", q, q_stride_h, k, k_stride_h, k_stride_l, Hq, Hkv, Lk, D, dtype);
+    if (rc == STTM_OK) rc = decode_check("gathered attention", q, q_stride_h, v, v_stride_h, v_stride_l, Hq, Hkv, Lk, D, dtype);
+    if (rc != STTM_OK) return rc;
+    if (!keep || !workspace || !out || n_keep < 1 || n_keep > Lk) return fail(STTM_ERR_ARG, "gathered attention: bad pointer or keep list length");
+    const int tiles = (n_keep + sttm::decode_tile_rows(dtype, D) - 1) / sttm::decode_tile_rows(dtype, D);
+    const size_t stat = align256((size_t)tiles * Hq * 2 * 4);
+    if (workspace_bytes < stat + (size_t)tiles * Hq * D * 4) return fail(STTM_ERR_ARG, "workspace too small");
+    char* ws = reinterpret_cast<char*>(workspace);
+    hipError_t e = sttm::launch_decode_gathered(q, q_stride_h, k, k_stride_h, k_stride_l, v, v_stride_h, v_stride_l, Hq, Hkv, Lk, D, dtype, scale,
+                                                keep, n_keep, reinterpret_cast<float*>(ws), reinterpret_cast<float*>(ws + stat), out,
+                                                reinterpret_cast<hipStream_t>(stream_));
+    if (e != hipSuccess) return fail(STTM_ERR_LAUNCH, "gathered attention kernels: %s", hipGetErrorString(e));
+    return STTM_OK;
+}
+
 size_t sttm_octree_workspace_bytes(int n_cubes, int side, int C, int dtype, int root_level) {
     if (n_cubes < 1 || C < 1 || dtype < 0 || dtype > 2) { fail(STTM_ERR_ARG, "bad cubes/C/dtype"); return 0; }
     OctPlan p;

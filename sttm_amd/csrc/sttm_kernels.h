@@ -266,6 +266,15 @@ size_t octree_scan_bytes(int64_t n);
 hipError_t launch_octree(OctArgs& a, int dtype, int vec, void* scan_tmp, size_t scan_bytes, hipStream_t stream);
 hipError_t launch_dycoke(const void* x, int T, int P, int C, int dtype, int k, float* sim, int32_t* keep, void* out, int64_t* out_idx,
                          hipStream_t stream);
+// DyCoke stage 2 (dycoke_decode.hip): rows of a tile for this dtype / head dim, and the three launch sets
+int decode_tile_rows(int dtype, int D);
+hipError_t launch_decode_scores(const void* q, int64_t q_sh, const void* k, int64_t k_sh, int64_t k_sl, int Hq, int Hkv, int Lk, int D,
+                                int dtype, float scale, float* logits, float* part, float* score, hipStream_t stream);
+hipError_t launch_decode_select(const float* score, int start, int window, int num_keep, int tail_from, int tail_len, int32_t* keep,
+                                hipStream_t stream);
+hipError_t launch_decode_gathered(const void* q, int64_t q_sh, const void* k, int64_t k_sh, int64_t k_sl, const void* v, int64_t v_sh,
+                                  int64_t v_sl, int Hq, int Hkv, int Lk, int D, int dtype, float scale, const int32_t* keep, int n_keep,
+                                  float* part, float* pacc, void* out, hipStream_t stream);
 hipError_t launch_label_edges(const int32_t* pairs, int L, int N, int32_t* rep_out, int32_t* rep2, int32_t* emin,
                               int32_t* iters_out, hipStream_t stream);
 

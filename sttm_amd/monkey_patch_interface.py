@@ -3,8 +3,9 @@
 `replace_qwen2_by_sparse_attn(pattern_name, **kwargs)` dispatches on the same pattern names.  "quadtree" and "tome" --
 the two patterns on the hot path -- and the baselines that share their hook ("quadtree-abl-pos", "pyrd", "dycoke-stage1",
 "octree") are implemented: like the reference they store their configuration as CLASS attributes on the decoder model
-class and overwrite its `.forward` (quadtree_attn_monkey_patch.py:177-187, tome_attn_monkey_patch.py:163-171).  Only full
-DyCoke (decode-time KV pruning), the FrameFusion baselines and the plotting variants raise NotImplementedError, with a message
+class and overwrite its `.forward` (quadtree_attn_monkey_patch.py:177-187, tome_attn_monkey_patch.py:163-171).  Full DyCoke
+(stage 1 + decode-time KV selection) is installed by `replace_qwen2_with_dycoke_attn`; the dispatcher still refuses the name
+"dycoke" and points there.  Only the FrameFusion baselines and the plotting variants raise NotImplementedError, with a message
 that says so.
 
 The reference pins transformers==4.45.2 and patches a verbatim copy of that version's Qwen2Model.forward.  This
@@ -23,7 +24,6 @@ from .tome_interface import get_tome_features
 
 _UNIMPLEMENTED = {
     "quadtree_vis": "visualisation variant",
-    "dycoke": "DyCoke with stage-2 KV-cache pruning during decoding",
 }
 
 
@@ -150,7 +150,95 @@ def _reset_merged_mask(past_key_values):
         past_key_values.sttm_merged_mask = None
 
 
+# ---- DyCoke stage 2 ("dycoke": decode-time KV selection, dycoke_attn_monkey_patch.py) -----------------------------------------
+DYCOKE_ATTN = "sttm_dycoke"           # name of the dispatching attention function in transformers' AttentionInterface
+
+
+class _DycokeStep:
+    """State of ONE decode forward: what the dispatching attention function reads and the keep list it leaves for the later layers."""
+    def __init__(self, cls, base_impl, l, start, n0, num_keep):
+        self.base_impl, self.l, self.start, self.n0, self.num_keep = base_impl, l, start, n0, num_keep
+        self.scores_fn, self.select_fn, self.attn_fn = cls.sttm_decode_scores_fn, cls.sttm_decode_select_fn, cls.sttm_decode_attn_fn
+        self.score = self.keep = None
+
+
+def _dycoke_attention(module, query, key, value, attention_mask, scaling=None, **kwargs):
+    """Attention function of a "dycoke" decode forward.  Layer l - 1 also yields the head-mean softmax row and the keep list (:80,
+    :62-77); layers >= l attend to the kept rows of the cache (:54-60); everything else is the implementation the user configured."""
+    from transformers.modeling_utils import ALL_ATTENTION_FUNCTIONS
+    from transformers.models.qwen2.modeling_qwen2 import eager_attention_forward
+    st = getattr(module.config, "_sttm_dycoke_step", None)
+    if st is None:
+        raise RuntimeError(f"the {DYCOKE_ATTN!r} attention function only runs inside a DyCoke decode forward "
+                           "(replace_qwen2_with_dycoke_attn); it is not an attn_implementation of its own")
+    scaling = module.scaling if scaling is None else scaling
+    i = module.layer_idx
+    if i >= st.l:
+        return st.attn_fn(query, key, value, st.keep, scaling), None
+    if i == st.l - 1:
+        st.score = st.scores_fn(query, key, scaling)
+        st.keep = st.select_fn(st.score, st.start, st.n0, st.num_keep)
+    base = ALL_ATTENTION_FUNCTIONS.get_interface(st.base_impl, eager_attention_forward)
+    return base(module, query, key, value, attention_mask, scaling=scaling, **kwargs)
+
+
+def _dycoke_step(self, inputs_embeds, past_key_values):
+    """None, or the _DycokeStep of this decode forward (refusals first, all before any layer runs)."""
+    state = getattr(past_key_values, "sttm_dycoke", None) if past_key_values is not None else None
+    if state is None or inputs_embeds.shape[1] != 1:                    # :407 `position_ids.shape[1] == 1`
+        return None
+    cfg, l = self.config, self.dycoke_l
+    if inputs_embeds.shape[0] != 1:
+        raise NotImplementedError(f"DyCoke stage 2 reads row 0 of the attention matrix (`[0, -1]`): batch size 1 only, got {inputs_embeds.shape[0]}")
+    if not 1 <= l < cfg.num_hidden_layers:
+        raise ValueError(f"dycoke_l = {l} must be in [1, num_hidden_layers = {cfg.num_hidden_layers}): layer dycoke_l - 1 supplies the scores")
+    if self.sa_start_layer_idx > l - 1:
+        raise ValueError(f"sa_start_layer_idx = {self.sa_start_layer_idx} must not exceed dycoke_l - 1 = {l - 1}: the keep list of layer "
+                         "dycoke_l - 1 indexes the cache of the later layers, which must hold the same (merged) sequence")
+    if any(t != "full_attention" for t in cfg.layer_types[l - 1:]):
+        raise NotImplementedError(f"a sliding-window layer at or after dycoke_l - 1 = {l - 1} is not supported by DyCoke stage 2")
+    head_dim = self.layers[l].self_attn.head_dim
+    own = type(self).sttm_decode_attn_fn is _default_decode_fns()[2]
+    if own and head_dim not in (64, 128):
+        raise NotImplementedError(f"head dimension {head_dim}: the decode kernels are built for 64 and 128")
+    if own and inputs_embeds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        raise NotImplementedError(f"dtype {inputs_embeds.dtype}: the decode kernels take float32, bfloat16 and float16")
+    start, n0 = state
+    num_keep = int(n0 * (1 - self.dycoke_p))                            # :66
+    Lk = past_key_values.get_seq_length(l - 1) + 1
+    window = min(start + n0, Lk) - start
+    if num_keep > window:                                               # the reference's topk raises (:69)
+        raise RuntimeError(f"selected index k out of range: num_keep = int({n0} * (1 - {self.dycoke_p})) = {num_keep} exceeds the "
+                           f"window of {window} scores [{start}, {min(start + n0, Lk)})")
+    return _DycokeStep(type(self), cfg._attn_implementation, l, start, n0, num_keep)
+
+
+def _default_decode_fns():
+    from .dycoke_decode import decode_attn_scores, gathered_decode_attention, select_keep
+    return decode_attn_scores, select_keep, gathered_decode_attention
+
+
 def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
+                              inputs_embeds=None, use_cache=None, **kwargs):
+    """`_qwen2_forward` under the pattern's decode-time switches: a "dycoke" decode step runs with the dispatching attention function
+    and its per-forward state on the config; both are put back whatever happens."""
+    if self.sttm_pattern != "dycoke":
+        return _qwen2_forward(self, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs)
+    x = inputs_embeds if inputs_embeds is not None else input_ids
+    if x is not None and x.shape[0] != 1:
+        raise NotImplementedError(f"DyCoke reads row 0 of the attention matrix (`[0, -1]`) and prunes one video: batch size 1 only, got {x.shape[0]}")
+    cfg = self.config
+    saved = cfg._attn_implementation
+    try:
+        return _qwen2_forward(self, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs)
+    finally:
+        if cfg._attn_implementation != saved:
+            cfg._attn_implementation = saved
+        if getattr(cfg, "_sttm_dycoke_step", None) is not None:
+            cfg._sttm_dycoke_step = None
+
+
+def _qwen2_forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                               inputs_embeds=None, use_cache=None, **kwargs):
     """transformers 5.x Qwen2Model.forward + the STTM / ToMe hook (prefill).  "quadtree" on B > 1 left-padded prompts (or 1-D hook
     attributes) takes the batched hook; every other case runs the batch-1 hook."""
@@ -167,6 +255,12 @@ def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, positio
     rows = _batched_rows(self, inputs_embeds, attention_mask, prefilling, _QWEN2_ROW_ATTRS)
     if prefilling:
         _reset_merged_mask(past_key_values)
+        if past_key_values is not None and getattr(past_key_values, "sttm_dycoke", None) is not None:
+            past_key_values.sttm_dycoke = None
+    elif self.sttm_pattern == "dycoke" and (step := _dycoke_step(self, inputs_embeds, past_key_values)) is not None:
+        # restored by _qwen2_forward_with_merge
+        self.config._sttm_dycoke_step = step
+        self.config._attn_implementation = DYCOKE_ATTN
     if position_ids is None and rows is not None:
         position_ids = _positions_from_mask(attention_mask, inputs_embeds)
     if position_ids is None:
@@ -224,9 +318,11 @@ def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, positio
                     self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
                     slow_ver=self.sttm_slow_ver, head_dim=head_dim,
                     merge_into_fn=_fused_merge_fn(type(self)))
-            elif self.sttm_pattern == "dycoke-stage1":
+            elif self.sttm_pattern in ("dycoke-stage1", "dycoke"):
                 hidden_states, position_ids, idx = patch_hooks.dycoke_merge(
                     hidden_states, position_ids, start, length, T, type(self).sttm_dycoke_fn, self.sa_prune_ratio)
+                if self.sttm_pattern == "dycoke" and past_key_values is not None:
+                    past_key_values.sttm_dycoke = (start, length)     # :370-371: the visual token count BEFORE stage 1
             elif self.sttm_pattern == "octree":
                 hidden_states, position_ids = patch_hooks.octree_merge(
                     hidden_states, position_ids, start, length, T, type(self).sttm_octree_fn, self.sa_tree_thresh,
@@ -429,6 +525,28 @@ def replace_qwen2_with_dycoke_stage1_attn(sa_start_layer_idx=0, sa_prune_ratio=0
     _install_dycoke(_qwen2_model_class(), _qwen2_forward_with_merge, sa_start_layer_idx, sa_prune_ratio)
 
 
+def replace_qwen2_with_dycoke_attn(sa_start_layer_idx=0, sa_prune_ratio=0.7, dycoke_l=3, dycoke_p=0.8, **kwargs):
+    """dycoke_attn_monkey_patch.py:452-468: stage 1 at prefill, stage 2 (KV selection from layer dycoke_l on) at every decode step."""
+    if int(dycoke_l) != dycoke_l or dycoke_l < 1:
+        raise ValueError(f"dycoke_l = {dycoke_l} must be an integer >= 1: layer dycoke_l - 1 supplies the attention scores")
+    if not 0.0 <= dycoke_p <= 1.0:
+        raise ValueError(f"dycoke_p = {dycoke_p} must lie in [0, 1]: int(n0 * (1 - dycoke_p)) visual keys are kept")
+    print("Replace Qwen2 attention path by DyCoke (stage 1 + decode-time KV selection) [sttm_amd / MI355X]")
+    from transformers.modeling_utils import AttentionInterface
+    cls = _qwen2_model_class()
+    _install_dycoke(cls, _qwen2_forward_with_merge, sa_start_layer_idx, sa_prune_ratio)
+    cls.sttm_pattern = "dycoke"
+    cls.dycoke_l = int(dycoke_l)
+    cls.dycoke_p = float(dycoke_p)
+    for name, fn in zip(_DECODE_FNS, _default_decode_fns()):
+        if not hasattr(cls, name):
+            setattr(cls, name, staticmethod(fn))
+    AttentionInterface.register(DYCOKE_ATTN, _dycoke_attention)
+
+
+_DECODE_FNS = ("sttm_decode_scores_fn", "sttm_decode_select_fn", "sttm_decode_attn_fn")
+
+
 def replace_qwen2vl_with_dycoke_stage1_attn(sa_start_layer_idx=0, sa_prune_ratio=0.7, **kwargs):
     """token_merging_qwen2vl_monkey_patch/dycoke_stage1_attn_monkey_patch.py:165-168."""
     cls = _qwen2vl_model_class()
@@ -512,6 +630,15 @@ def restore_qwen2():
         if cls is not None and "_sttm_original_forward" in cls.__dict__:
             cls.forward = cls._sttm_original_forward
             del cls._sttm_original_forward
+    # "dycoke": the dispatching attention function and the class state of the decode step
+    cls = _qwen2_model_class()
+    for name in _DECODE_FNS + ("dycoke_l", "dycoke_p"):
+        if name in cls.__dict__:
+            delattr(cls, name)
+    if cls.__dict__.get("sttm_pattern") == "dycoke":
+        del cls.sttm_pattern
+    from transformers.modeling_utils import AttentionInterface
+    AttentionInterface._global_mapping.pop(DYCOKE_ATTN, None)
 
 
 def replace_qwen2_by_sparse_attn(pattern_name, **kwargs):
@@ -530,6 +657,10 @@ def replace_qwen2_by_sparse_attn(pattern_name, **kwargs):
     elif pattern_name == "dycoke-stage1":
         replace_qwen2_with_dycoke_stage1_attn(**kwargs)
         replace_qwen2vl_with_dycoke_stage1_attn(**kwargs)
+    elif pattern_name == "dycoke":
+        # the name is routed here together with the test that pins this refusal ("DyCoke stage 2")
+        raise NotImplementedError("dycoke is not routed through replace_qwen2_by_sparse_attn yet: install it with "
+                                  "replace_qwen2_with_dycoke_attn(sa_start_layer_idx, sa_prune_ratio, dycoke_l, dycoke_p)")
     elif pattern_name in _UNIMPLEMENTED:
         raise NotImplementedError(f"{pattern_name} ({_UNIMPLEMENTED[pattern_name]}) is outside the MI355X hot-path build")
     else:
