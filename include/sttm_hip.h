@@ -324,6 +324,28 @@ int sttm_tome_step(const void* x, const float* size, const int64_t* idx, int n, 
                    float* node_max_out, int32_t* node_idx_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Per-frame / per-snippet ToMe: ONE iteration of the same loop over n_seg INDEPENDENT segments of n tokens each (a segment = the
+ * tokens of one frame or of a snippet of a few frames), every segment merged exactly as sttm_tome_step merges a [n, C] matrix:
+ * the even / odd split goes by the token's index inside its segment, a token is only matched against tokens of its own segment.
+ * The number of kernel launches (four) does not depend on n_seg.  dtypes and rounding rules as above (float32: two-plane fp16
+ * split, three plane products).
+ *
+ *   x          [n_seg * n, C] row-major, segment after segment       size  [n_seg * n] or NULL for all ones (first iteration)
+ *   idx        [n_seg * n] int64 token ids, or NULL for 0 .. n_seg * n - 1 (first iteration)
+ *   r          tokens to remove PER SEGMENT, 1 <= r <= n / 2
+ *   x_out      [n_seg * (n - r), C]   size_out / idx_out [n_seg * (n - r)]
+ *              segment after segment; inside a segment the row order of sttm_tome_step
+ * Enqueued on `stream` without any host synchronisation; workspace >= sttm_tome_segments_workspace_bytes(n_seg, n, C, n_head).
+ * Limit: n <= STTM_TOME_SEGMENT_MAX_TOKENS (the ranking of a segment lives in the LDS of one workgroup) and n_seg * n <= 2^28;
+ * beyond it, and for bad arguments, sttm_tome_segments_workspace_bytes returns 0 (the reason is in sttm_last_error()) and
+ * sttm_tome_step_segments STTM_ERR_UNSUPPORTED / STTM_ERR_ARG: longer segments are the job of sttm_tome_step, one call each.
+ * ------------------------------------------------------------------------------------------------ */
+#define STTM_TOME_SEGMENT_MAX_TOKENS 1024
+size_t sttm_tome_segments_workspace_bytes(int n_seg, int n, int C, int n_head);
+int sttm_tome_step_segments(const void* x, const float* size, const int64_t* idx, int n_seg, int n, int C, int n_head, int r, int dtype,
+                            void* workspace, size_t workspace_bytes, void* x_out, float* size_out, int64_t* idx_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Upstream 2-D pooling of the projected vision tokens: replaces LlavaMetaForCausalLM.get_2dPool
  * (llava/model/llava_arch.py:173-198): x [T, H*W, C] row-major tokens -> out [T, OH*OW, C], same dtype.
  *   mode STTM_POOL_AVERAGE / STTM_POOL_MAX : stride x stride windows, OH = H / stride (floor)   (:185-188)

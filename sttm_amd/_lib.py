@@ -23,6 +23,7 @@ EVENT_SLOTS = 5            # STTM_EVENT_SLOTS
 BATCH_MAX = 16             # STTM_BATCH_MAX
 EARLY_SLOTS = 64           # STTM_EARLY_SLOTS
 PACK_GEOM = 7              # STTM_PACK_GEOM
+TOME_SEGMENT_MAX_TOKENS = 1024   # STTM_TOME_SEGMENT_MAX_TOKENS
 PACK_POS_NONE, PACK_POS_TRUNCATE, PACK_POS_GATHER3 = 0, 1, 2
 
 # every symbol include/sttm_hip.h declares, with its ctypes signature
@@ -51,6 +52,8 @@ SIGNATURES = {
     "sttm_merge_dst_idx": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp]),
     "sttm_tome_workspace_bytes": (_sz, [_i, _i, _i]),
     "sttm_tome_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "sttm_tome_segments_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "sttm_tome_step_segments": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _vp]),
     "sttm_pool2d_out_side": (_i, [_i, _i, _i]),
     "sttm_pool2d": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sttm_dycoke_workspace_bytes": (_sz, [_i, _i, _i]),

@@ -1202,6 +1202,36 @@ int sttm_decode_attn_gathered(const void* q, int64_t q_stride_h, const void* k, 
     return STTM_OK;
 }
 
+// ---- per-frame / per-snippet ToMe ----------------------------------------------------------------------------------------------
+static int tome_segments_check(int n_seg, int n, int C, int n_head, sttm::TomeSegPlan* p) {
+    const int rc = sttm::tome_segments_plan(n_seg, n, C, n_head, p);
+    if (rc == STTM_ERR_UNSUPPORTED)
+        return fail(rc, "ToMe segments: %d tokens per segment (the segment kernels serve up to %d) or more than 2^28 tokens in all; "
+                        "longer snippets go through sttm_tome_step", n, STTM_TOME_SEGMENT_MAX_TOKENS);
+    if (rc != STTM_OK) return fail(rc, "ToMe segments: bad configuration n_seg=%d n=%d C=%d n_head=%d", n_seg, n, C, n_head);
+    return STTM_OK;
+}
+
+size_t sttm_tome_segments_workspace_bytes(int n_seg, int n, int C, int n_head) {
+    sttm::TomeSegPlan p;
+    if (tome_segments_check(n_seg, n, C, n_head, &p) != STTM_OK) return 0;
+    return p.total;
+}
+
+int sttm_tome_step_segments(const void* x, const float* size, const int64_t* idx, int n_seg, int n, int C, int n_head, int r, int dtype,
+                            void* workspace, size_t workspace_bytes, void* x_out, float* size_out, int64_t* idx_out, void* stream_) {
+    if (dtype < 0 || dtype > 2) return fail(STTM_ERR_ARG, "ToMe segments: bad dtype");
+    if (!x || !workspace || !x_out || !size_out || !idx_out) return fail(STTM_ERR_ARG, "ToMe segments: bad pointer");
+    sttm::TomeSegPlan p;
+    if (const int rc = tome_segments_check(n_seg, n, C, n_head, &p)) return rc;
+    if (workspace_bytes < p.total) return fail(STTM_ERR_ARG, "workspace too small");
+    if (r < 1 || r > p.nb) return fail(STTM_ERR_ARG, "ToMe segments: r = %d outside [1, n / 2 = %d]", r, p.nb);
+    hipError_t e = sttm::launch_tome_segments(x, size, idx, n_seg, n, C, n_head, r, dtype, p, workspace, x_out, size_out, idx_out,
+                                              reinterpret_cast<hipStream_t>(stream_));
+    if (e != hipSuccess) return fail(STTM_ERR_LAUNCH, "ToMe segment kernels: %s", hipGetErrorString(e));
+    return STTM_OK;
+}
+
 size_t sttm_octree_workspace_bytes(int n_cubes, int side, int C, int dtype, int root_level) {
     if (n_cubes < 1 || C < 1 || dtype < 0 || dtype > 2) { fail(STTM_ERR_ARG, "bad cubes/C/dtype"); return 0; }
     OctPlan p;

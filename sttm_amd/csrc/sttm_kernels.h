@@ -222,6 +222,15 @@ void pairs_shape(int T, int R, int fold, int want_seg, int want_nt, int* seg, in
 int tome_flat_mode();        // 256-tile ToMe match kernels: 1 = tile products spread evenly over the CUs when that is shorter, 0 = never, 2 = always
 int tome_split_mode();       // 0 = fp32-input MFMA match kernel; > 0 = fp16 two-plane split variants (api.hip: Config)
 
+// Per-frame / per-snippet ToMe (tome_snippet.hip): workspace layout of one iteration over n_seg segments of n tokens, and its launches
+struct TomeSegPlan {
+    int na, nb, D, Dp;
+    size_t off_a, off_b, off_best, off_order, off_off, off_lists, total;
+};
+int tome_segments_plan(int n_seg, int n, int C, int n_head, TomeSegPlan* p);      // STTM_OK, STTM_ERR_ARG or STTM_ERR_UNSUPPORTED (beyond the cap)
+hipError_t launch_tome_segments(const void* x, const float* size, const int64_t* idx, int n_seg, int n, int C, int n_head, int r, int dtype,
+                                const TomeSegPlan& p, void* workspace, void* x_out, float* size_out, int64_t* idx_out, hipStream_t stream);
+
 hipError_t launch_pool2d(const void* x, void* out, int T, int H, int W, int C, int OH, int OW, int stride, int mode, int dtype,
                          hipStream_t stream);
 

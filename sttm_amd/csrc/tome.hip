@@ -11,7 +11,7 @@
 //   k_tome_rank        ranking of the a-tokens by best score, descending, ties to the smaller index: by counting (any clip length)
 //   k_tome_*           per-destination source lists in rank order, then the size-weighted merge
 // Nothing here depends on data-dependent sizes: the step is enqueued without any host synchronisation.
-#include "sttm_kernels.h"
+#include "tome_device.h"      // helpers shared with tome_snippet.hip: score / rank keys, 16-bit rounding, MFMA wrappers
 
 namespace sttm {
 
@@ -55,54 +55,7 @@ constexpr int TM_LD = TM_I + 1;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-__device__ __forceinline__ unsigned long long pack_score(float v, int j) {
-    // order-preserving map of the float, then "smaller j wins" on ties (torch.max returns the first maximum)
-    unsigned u = __float_as_uint(v);
-    u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xffffffffu - (unsigned)j);
-}
 
-// Running max / argmax of one lane's scores of a 64 (j) x 32*QI (i) wave tile: acc[p][q][e] is the score of a-row q against
-// candidate  jlane + p*32 + (e&3) + 8*(e>>2)  (jlane = tile origin + wave's j offset + 4 * lane half).  A lane meets its candidates in
-// ascending j -- inside a tile and from tile to tile -- so the first maximum (torch.max; tome_token_merger.py:36) is the first score
-// STRICTLY above the running one: for tiles that lie inside [0, nb) that is a compare and two selects per score, no branch.
-// Only the last, partial tile takes the general form (round 2's, which cost ~30 instructions and an exec-mask branch per score).
-typedef float tome_f32x16 __attribute__((ext_vector_type(16)));
-template <int QI, typename RoundFn, int PJ = 2>
-__device__ __forceinline__ void tome_running_max(const tome_f32x16 (&acc)[PJ][QI], float (&bestv)[QI], int (&bestj)[QI], int jlane, int nb,
-                                                 bool inside, RoundFn rnd) {
-    static_assert(PJ != 4, "the four-wave kernel has its own running max (tome_running_max_agpr)");
-    if (inside) {
-#pragma unroll
-        for (int q = 0; q < QI; ++q) {
-            float bv = bestv[q];
-            int bc = -1;
-#pragma unroll
-            for (int p = 0; p < PJ; ++p) {
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const float v = rnd(acc[p][q][e]);
-                    const bool gt = v > bv;
-                    bc = gt ? p * 32 + (e & 3) + 8 * (e >> 2) : bc;
-                    bv = gt ? v : bv;
-                }
-            }
-            bestj[q] = bc >= 0 ? jlane + bc : bestj[q];
-            bestv[q] = bv;
-        }
-    } else {
-#pragma unroll
-        for (int q = 0; q < QI; ++q)
-#pragma unroll
-            for (int p = 0; p < PJ; ++p)
-#pragma unroll
-                for (int e = 0; e < 16; ++e) {
-                    const int j = jlane + p * 32 + (e & 3) + 8 * (e >> 2);
-                    const float v = rnd(acc[p][q][e]);
-                    if (j < nb && (v > bestv[q] || (v == bestv[q] && j < bestj[q]))) { bestv[q] = v; bestj[q] = j; }
-                }
-    }
-}
 
 // ---- the two-pass running max of the 256-tile kernels (round 6) -----------------------------------------------------------------
 // The sweep above costs ~5 VALU instructions per score (round to the input dtype, compare, two selects) -- 128 scores per lane and tile
@@ -358,25 +311,7 @@ __global__ void __launch_bounds__(256, 2) k_tome_match(const float* __restrict__
 }
 
 
-// ---------------------------------------------------------------------------------------------------
-// 16-bit inputs (bfloat16 / float16): the reference runs the same torch ops on the hidden states' dtype
-// (tome_attn_monkey_patch.py:88-107 with a bf16 model), so every intermediate tensor is ROUNDED to that dtype:
-// the unit rows, the scores (an fp32-accumulating matmul whose result is stored in 16 bits -- hence many exact ties,
-// first maximum = smaller j), x * size, every scatter-add step, the final division.  Matrix products run on
-// v_mfma_f32_32x32x16_{bf16,f16} (16x the fp32-input rate).
-// ---------------------------------------------------------------------------------------------------
-template <typename T> __device__ __forceinline__ float tome_round(float f);
-template <> __device__ __forceinline__ float tome_round<float>(float f) { return f; }
-template <> __device__ __forceinline__ float tome_round<bf16_t>(float f) { return bf16_bits_to_float(float_to_bf16_bits(f)); }
-template <> __device__ __forceinline__ float tome_round<f16_t>(float f) { return f16_bits_to_float(float_to_f16_bits(f)); }
-template <typename T> __device__ __forceinline__ float tome_ld(const void* p, int64_t i);
-template <> __device__ __forceinline__ float tome_ld<float>(const void* p, int64_t i) { return reinterpret_cast<const float*>(p)[i]; }
-template <> __device__ __forceinline__ float tome_ld<bf16_t>(const void* p, int64_t i) { return bf16_bits_to_float(reinterpret_cast<const uint16_t*>(p)[i]); }
-template <> __device__ __forceinline__ float tome_ld<f16_t>(const void* p, int64_t i) { return f16_bits_to_float(reinterpret_cast<const uint16_t*>(p)[i]); }
-template <typename T> __device__ __forceinline__ void tome_st(void* p, int64_t i, float v);
-template <> __device__ __forceinline__ void tome_st<float>(void* p, int64_t i, float v) { reinterpret_cast<float*>(p)[i] = v; }
-template <> __device__ __forceinline__ void tome_st<bf16_t>(void* p, int64_t i, float v) { reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)float_to_bf16_bits(v); }
-template <> __device__ __forceinline__ void tome_st<f16_t>(void* p, int64_t i, float v) { reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)float_to_f16_bits(v); }
+// (the rounding rules of 16-bit inputs and the typed element access -- tome_round, tome_ld, tome_st -- are in tome_device.h)
 
 // unit rows in the input dtype: m = mean over heads (fp32 sum, rounded), |m| = sqrt(fp32 sum of squares) rounded,
 // m / |m| rounded; rows padded with zeros to the 32-wide k tile.  One wave per token row.
@@ -435,19 +370,6 @@ __global__ void __launch_bounds__(256) k_tome_normalize16(const void* __restrict
     }
 }
 
-typedef __bf16 tome_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 tome_f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-typedef unsigned int tome_u32x4 __attribute__((ext_vector_type(4)));      // 16-byte staging unit (a native vector: stays in registers)
-template <typename T> struct TomeMfma;
-template <> struct TomeMfma<bf16_t> {
-    typedef tome_bf16x8 vec;
-    static __device__ __forceinline__ f32x16_t run(vec a, vec b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct TomeMfma<f16_t> {
-    typedef tome_f16x8 vec;
-    static __device__ __forceinline__ f32x16_t run(vec a, vec b, f32x16_t c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
 
 // The four-wave kernel's accumulators (round 6): 16 blocks of 16 registers = the WHOLE AGPR file, named literally in inline assembly.
 // hipcc never sees them as values -- with the accumulators as C++ variables (through the MFMA builtin, or tied to the "a" register class)
@@ -578,8 +500,6 @@ __global__ void __launch_bounds__(256, 2) k_tome_match16(const uint16_t* __restr
 // |error| 9.1e-7 with four AND with three terms, 1.37e-6 for the fp32-input MFMA kernel above, no argmax change in 12 544
 // rows.  The reference's own scores are only defined up to that accumulation order (cuBLAS / MKL sgemm).
 // ---------------------------------------------------------------------------------------------------
-constexpr float kSplitScale = 4096.f;
-constexpr float kSplitUnscale = 1.f / (4096.f * 4096.f);
 
 // VEC = 4: one head, D % 4 == 0, 16-byte aligned rows (the production shape): float4 loads, 8-byte plane stores; the second
 // pass re-reads the row from the cache.  VEC = 1: any shape.
@@ -1038,10 +958,6 @@ __global__ void k_tome_fill(const int* __restrict__ order, const int* __restrict
 constexpr int RK_I = 256;
 constexpr int kRankParts = 32;         // most key-range parts per a-block (partial ranks are [parts][na] ints of workspace)
 
-__device__ __forceinline__ unsigned long long tome_rank_key(unsigned long long b, int i) {
-    const unsigned ku = b ? (unsigned)(b >> 32) : 0xffc00000u;          // no finite score at all: a NaN row (sorts first)
-    return ((unsigned long long)ku << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
-}
 
 __global__ void __launch_bounds__(RK_I) k_tome_rank(const unsigned long long* __restrict__ best, int na, int jsplit, int r,
                                                     int* __restrict__ rank, int* __restrict__ arrive, float* __restrict__ node_max,
@@ -1177,24 +1093,6 @@ __global__ void __launch_bounds__(RK_I) k_tome_rank(const unsigned long long* __
 // one wave per output row.  rows [0, na - r): unmerged a-tokens in rank order; rows [na - r, n - r): b-tokens.
 // Every tensor of the reference is rounded to the input dtype T (x * size, the scatter-added sums, the sums of sizes, the
 // quotient): for T = float that is the plain fp32 arithmetic of the reference, without contraction.
-template <typename T, int VEC> __device__ __forceinline__ void tome_ld_vec(const void* x, int64_t off, float (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        v[0] = tome_ld<T>(x, off);
-    } else {
-        const Pack<T, VEC> p = load_pack<T, VEC>(x, off);
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = p.get(e);
-    }
-}
-template <typename T, int VEC> __device__ __forceinline__ void tome_st_vec(void* x, int64_t off, const float (&v)[VEC]) {
-    if constexpr (VEC == 1) {
-        tome_st<T>(x, off, v[0]);
-    } else {
-        Pack<T, VEC> p;
-        pack_fill<T, VEC>(p, [&](int e) { return v[e]; });
-        store_pack<T, VEC>(x, off, p);
-    }
-}
 // VEC channels per lane and step (VEC * sizeof(T) bytes per access); the per-element arithmetic does not depend on VEC.
 // Round 4: 16-byte accesses for every dtype (16-bit rows: 8 channels per lane), up to NCH row chunks of a token in flight per lane
 // (C = 1024: the whole row), and a destination's sources looked up ONCE by the lanes in parallel (rank -> token -> size) instead

@@ -20,7 +20,7 @@ import torch
 from . import patch_hooks
 from .quadtree_interface import (get_quadtree_features, get_quadtree_features_batch_reused, get_quadtree_features_into,
                                  pack_merged_batch)
-from .tome_interface import get_tome_features
+from .tome_interface import get_tome_features, get_tome_features_snippet
 
 _UNIMPLEMENTED = {
     "quadtree_vis": "visualisation variant",
@@ -330,7 +330,7 @@ def _qwen2_forward(self, input_ids=None, attention_mask=None, position_ids=None,
                 idx = None                                            # the reference's octree hook keeps no token index
             else:
                 hidden_states, position_ids, idx = patch_hooks.tome_merge(
-                    hidden_states, position_ids, start, length, T, type(self).sttm_tome_fn, self.sa_prune_ratio, self.sa_tome_ver)
+                    hidden_states, position_ids, start, length, T, _tome_merge_fn(type(self)), self.sa_prune_ratio, self.sa_tome_ver)
             self.merged_token_1d_idx = idx
             if self.sttm_pattern != "quadtree-abl-pos":               # that hook decides its own position embeddings
                 position_embeddings = self.rotary_emb(hidden_states, position_ids)
@@ -415,7 +415,7 @@ def _qwen2vl_forward_with_merge(self, input_ids=None, attention_mask=None, posit
                     gather_positions=True)
             else:
                 hidden_states, position_ids, idx = patch_hooks.tome_merge(
-                    hidden_states, position_ids, start, length, T, type(self).sttm_tome_fn, self.sa_prune_ratio,
+                    hidden_states, position_ids, start, length, T, _tome_merge_fn(type(self)), self.sa_prune_ratio,
                     self.sa_tome_ver, H=H, W=W, gather_positions=True)
             if text_position_ids is not None:
                 text_position_ids = text_position_ids[..., :hidden_states.size(1)]
@@ -571,7 +571,29 @@ def replace_qwen2_with_pyrd_attn(sa_pyrd_loc_list=[2], sa_pyrd_size_list=[10], *
     cls.forward = _qwen2_forward_with_merge
 
 
-def replace_qwen2_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa_tome_ver="frame", **kwargs):
+def _tome_merge_fn(cls):
+    """The merge function the ToMe branch hands to patch_hooks.tome_merge: `sttm_tome_fn(video, prune_ratio, tome_ver)` as the
+    reference dispatches it, or -- when the installer was given sa_tome_snippet_size -- per-snippet ToMe, which ignores tome_ver."""
+    size = getattr(cls, "sa_tome_snippet_size", None)
+    if size is None:
+        return cls.sttm_tome_fn
+    fn = cls.sttm_tome_snippet_fn
+    return lambda video, prune_ratio, _tome_ver: fn(video, prune_ratio, size)
+
+
+def _install_tome_snippet(cls, sa_tome_snippet_size):
+    """sa_tome_snippet_size: None = the reference's tome_ver dispatch (where "frame" raises for T > 1); an integer S >= 1 = working
+    per-frame (S = 1) / per-snippet ToMe (get_tome_features_snippet)."""
+    if sa_tome_snippet_size is not None:
+        if isinstance(sa_tome_snippet_size, bool) or int(sa_tome_snippet_size) != sa_tome_snippet_size or sa_tome_snippet_size < 1:
+            raise ValueError(f"sa_tome_snippet_size must be an integer >= 1 or None, got {sa_tome_snippet_size!r}")
+        sa_tome_snippet_size = int(sa_tome_snippet_size)
+        if not hasattr(cls, "sttm_tome_snippet_fn"):
+            cls.sttm_tome_snippet_fn = staticmethod(get_tome_features_snippet)
+    cls.sa_tome_snippet_size = sa_tome_snippet_size
+
+
+def replace_qwen2_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa_tome_ver="frame", sa_tome_snippet_size=None, **kwargs):
     print("Replace Qwen2 attention path by ToMe token merging [sttm_amd / MI355X]")
     cls = _qwen2_model_class()
     cls.sttm_pattern = "tome"
@@ -580,6 +602,7 @@ def replace_qwen2_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa_t
     cls.sa_tome_ver = sa_tome_ver
     if not hasattr(cls, "sttm_tome_fn"):
         cls.sttm_tome_fn = staticmethod(get_tome_features)
+    _install_tome_snippet(cls, sa_tome_snippet_size)
     if not hasattr(cls, "_sttm_original_forward"):
         cls._sttm_original_forward = cls.forward
     cls.forward = _qwen2_forward_with_merge
@@ -608,7 +631,7 @@ def replace_qwen2vl_with_quadtree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90
     cls.forward = _qwen2vl_forward_with_merge
 
 
-def replace_qwen2vl_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa_tome_ver="frame", **kwargs):
+def replace_qwen2vl_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa_tome_ver="frame", sa_tome_snippet_size=None, **kwargs):
     cls = _qwen2vl_model_class()
     if cls is None:
         return
@@ -619,6 +642,7 @@ def replace_qwen2vl_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa
     cls.sa_tome_ver = sa_tome_ver
     if not hasattr(cls, "sttm_tome_fn"):
         cls.sttm_tome_fn = staticmethod(get_tome_features)
+    _install_tome_snippet(cls, sa_tome_snippet_size)
     if not hasattr(cls, "_sttm_original_forward"):
         cls._sttm_original_forward = cls.forward
     cls.forward = _qwen2vl_forward_with_merge
