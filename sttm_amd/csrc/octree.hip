@@ -93,8 +93,10 @@ __global__ void __launch_bounds__(256) k_oct_stop(const void* parent, const void
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
                 const double a = fmax((double)st[16], 1e-16), bb = fmax((double)st[8 + s], 1e-16);
-                const double d = (double)st[s];
-                all = all && (d * fabs(d) >= thr_lo_sq * (a * bb));
+                const double d = (double)st[s], ab = a * bb;
+                // a sum of squares that is +inf (an Inf element, fp32 overflow): NaN or 0 in the reference, as cosine_at_least
+                // (quadtree_spatial.inc) decides it
+                all = all && (ab < HUGE_VAL ? d * fabs(d) >= thr_lo_sq * ab : (thr_lo_sq <= 0.0 && fabs(d) < HUGE_VAL));
             }
             stop[cell] = all ? 1 : 0;
         }

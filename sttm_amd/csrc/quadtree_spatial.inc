@@ -462,10 +462,16 @@ __device__ __forceinline__ NodeLoc locate(const LevelDims& g, int I, int J, int 
 // is evaluated without sqrt/div: rounding to fp32 is monotonic, so it equals  sim >= lo  where lo is the smallest
 // real that rounds to >= thr (`thr_lo`, computed on the host in double), and  sim >= lo  <=>
 // dot*|dot| >= lo*|lo| * max(|p|^2, eps^2) * max(|c|^2, eps^2)   (the product of two fp32 values is exact in double).
+// A sum of squares that is +inf (an Inf element, or finite elements whose squares overflow fp32) would turn the test into
+// inf >= inf.  The reference divides every element by max(|x|, eps) = inf there: NaN when an element is Inf (inf / inf; dot is
+// then +-inf or NaN as well), 0 when only the norm overflowed -- never >= a positive threshold, and 0 >= lo for lo <= 0 only while
+// dot is finite (an infinite dot with lo <= 0 cannot be told apart from the sums alone and counts as the NaN case).
+// A NaN element needs nothing extra: fmax drops the NaN norm but dot is NaN, and NaN >= x is false.
 __device__ __forceinline__ bool cosine_at_least(float dot, float n2a, float n2b, double lo_sq_signed) {
     const double a = fmax((double)n2a, 1e-16), b = fmax((double)n2b, 1e-16);
-    const double d = (double)dot;
-    return d * fabs(d) >= lo_sq_signed * (a * b);
+    const double d = (double)dot, ab = a * b;
+    if (!(ab < HUGE_VAL)) return lo_sq_signed <= 0.0 && fabs(d) < HUGE_VAL;
+    return d * fabs(d) >= lo_sq_signed * ab;
 }
 
 // Same as locate() for a node whose depth DEPTH is known at compile time: every loop unrolls, the per-level

@@ -52,3 +52,33 @@ def iid_video(T, C, H, W, seed=0, dtype=torch.float32, device="cpu"):
     if device != "cpu":
         x = x.to(device)
     return x.permute(0, 3, 1, 2)
+
+
+def heavy_video(T, C=1024, H=14, W=14, seed=0, n_massive=6, scale=100.0, dtype=torch.float32, device="cpu"):
+    """Heavy-tailed, massive-activation family: synth-v1 times a heavy-tailed per-channel gain
+    |N(0,1)| / sqrt(mean of 3 squared normals) (a |t_3| variable: a few channels tens of times larger than the rest), with
+    `n_massive` channels overwritten by +-scale * (1 + 0.05 * randn) -- the shape of decoder hidden states, where a handful of
+    channels carries most of every token's norm and pushes all cosines towards 1.  Drawn on the CPU generator (seed = video id).
+
+    Two settings are in use (tests/_offdist.py HEAVY_SETTINGS), measured with the reference's arithmetic on T=16, 14x14 clips:
+      "massive"  n_massive=6, scale=100: the six channels dominate every token.  fp32 C=1024: every clip collapses to the 16 root
+                 cells at both presets (0.85/0.55 and 0.94/0.82).  bf16 C=3584 (the heavy-tailed rest carries more of the norm):
+                 16 nodes at 0.85/0.55, 20-25 nodes at 0.94/0.82.
+      "crowded"  n_massive=6, scale=HEAVY_CROWDED_SCALE[C]: calibrated per width so that the similarities crowd around the strict
+                 preset.  Of the 3136 tokens the reference keeps, at 0.94/0.82, 46-50 % (fp32 C=1024, scale 30) and 46-58 % (bf16
+                 C=3584, scale 55); at 0.85/0.55 20-21 nodes remain (seeds 0-3)."""
+    x = synth_video(T, C, H, W, seed=seed, dtype=torch.float32)
+    m = x.permute(0, 2, 3, 1)                                        # [T, H, W, C] memory
+    g = torch.Generator().manual_seed(int(seed) + 0x5EED)
+    gain = torch.randn(C, generator=g).abs() / torch.randn(3, C, generator=g).pow(2).mean(0).sqrt()
+    m.mul_(gain)
+    ch = torch.randperm(C, generator=g)[:n_massive]
+    sign = torch.randint(0, 2, (n_massive,), generator=g).float() * 2 - 1
+    m[..., ch] = sign * scale * (1.0 + 0.05 * torch.randn(T, H, W, n_massive, generator=g))
+    x = m.to(dtype)
+    if torch.device(device) != x.device:
+        x = x.to(device)
+    return x.permute(0, 3, 1, 2)
+
+
+HEAVY_CROWDED_SCALE = {1024: 30.0, 3584: 55.0}        # channel count -> scale of the "crowded" setting (heavy_video's docstring)
