@@ -143,8 +143,12 @@ __global__ void __launch_bounds__(1024) k_dycoke_select(DycokeArgs a, int npad) 
     float* key = reinterpret_cast<float*>(smem_raw);
     int* val = reinterpret_cast<int*>(key + npad);
     const int j = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
+    // A NaN similarity (a token with an Inf or NaN element: inf / inf in the normalise step) sorts as +inf, which no cosine is:
+    // topk(largest=False) takes such tokens last, and the comparison below stays a total order.  They tie with the padding
+    // entries and go ahead of them on the token id, so a pad id is never among the first k <= P.
     for (int i = tid; i < npad; i += nt) {
-        key[i] = i < a.P ? a.sim[(int64_t)j * a.P + i] : INFINITY;
+        const float s = i < a.P ? a.sim[(int64_t)j * a.P + i] : INFINITY;
+        key[i] = s != s ? INFINITY : s;
         val[i] = i < a.P ? i : 0x7fffffff;
     }
     __syncthreads();

@@ -120,7 +120,9 @@ __device__ __forceinline__ void dec_tile_softmax(int gn, float (*sl)[ROWS], floa
 #pragma unroll
         for (int j = 0; j < (ROWS + 63) / 64; ++j) {
             const int r = j * 64 + lane;
-            const float p = expf(x[j] - m);
+            // an invalid row contributes nothing, also where the whole tile is invalid (m = -inf: not exp(-inf + inf)).  Keyed on the
+            // row, not on m: fmaxf drops NaN, so a tile whose valid rows are all NaN has m = -inf too, and NaN - (-inf) stays NaN.
+            const float p = x[j] == -INFINITY ? 0.f : expf(x[j] - m);
             if (r < ROWS) sl[g][r] = p;
             s += p;
         }

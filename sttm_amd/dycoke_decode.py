@@ -49,8 +49,10 @@ def _check(q, k, what):
 def _rows16(t):
     """The tensor, or a contiguous copy when a row would not start on a 16-byte boundary."""
     eb = t.element_size()
-    if t.stride(-1) != 1 or t.data_ptr() % 16 or any((s * eb) % 16 for s in t.stride()[1:3]):
-        return t.contiguous()
+    if t.stride(-1) != 1 or any((s * eb) % 16 for s in t.stride()[1:3]):
+        t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone()              # contiguous already, but its storage starts off a 16-byte boundary: `.contiguous()` returns it as it is
     return t
 
 

@@ -2,7 +2,10 @@
 """Golden vectors for the DyCoke stage-1 baseline, made by RUNNING THE REFERENCE's `dycoke_ttm`
 (token_merging_utils/dycoke_merger.py:8-83) in the build container (CPU).  Only data is written.
 
-    python tests/golden/make_golden_dycoke.py        # rewrites tests/golden/dyc_*.npz
+    python tests/golden/make_golden_dycoke.py        # rewrites tests/golden/dyc_*.npz and tests/golden/dycod_*.npz
+
+dycod_*: the degenerate clips of tests/_dycoke_offdist.py (one Inf or NaN element, NaN tokens on either side of a pair, an all-zero
+token, two identical frames, fewer finite similarities than k), float32 and bfloat16: what `topk(largest=False)` does with NaN.
 """
 import json
 import os
@@ -19,6 +22,7 @@ sys.path.insert(0, REF)
 
 from sttm_amd.synth import synth_video                                  # noqa: E402
 from token_merging_utils.dycoke_merger import dycoke_ttm               # noqa: E402  (reference)
+from tests import _dycoke_offdist as DO                                 # noqa: E402
 
 CASES = [
     dict(name="dyc_t8_p196", T=8, side=14, C=64, prune=0.7, seed=1),
@@ -41,6 +45,14 @@ def main():
         np.savez_compressed(os.path.join(HERE, c["name"] + ".npz"), meta=json.dumps(meta), x=x.numpy(), feat=feat.numpy(),
                             idx=idx.numpy())
         print(c["name"], tuple(x.shape), "->", tuple(feat.shape))
+    for name, (_, prune) in DO.DEGENERATE.items():
+        for dname in DO.DEG_DTYPES:
+            fid = f"dycod_{name}_{DO.SHORT[dname]}"
+            x = DO.build_degenerate(name, dname)
+            feat, idx = dycoke_ttm(x, DO.DEG_T, prune)
+            meta = dict(name=fid, case=name, T=DO.DEG_T, side=DO.DEG_SIDE, C=DO.DEG_C, prune=prune, dtype=dname, fn="dycoke")
+            DO.save_dycod(fid, meta, x, feat, idx)
+            print(fid, tuple(x.shape), "->", tuple(feat.shape))
 
 
 if __name__ == "__main__":
