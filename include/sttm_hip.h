@@ -294,6 +294,17 @@ int sttm_quadtree_apply(const void* v, int64_t stride_t, int64_t stride_c, int64
                         const int32_t* counts, void* out, void* stream);
 
 /*
+ * The per-leaf maps of the merge that ran LAST on this stream with this workspace (the contract of sttm_quadtree_apply; same
+ * T / H / W / root_level, C_feat / dtype_feat are that call's feature width and dtype, needed to find the tables again):
+ *   token_to_out  [T*H*W] int32: row of feat_out the leaf was merged into, in [0, N')
+ *   token_to_node NULL, or [T*H*W] int32: origin row t*H*W + y1*W + x1 of the spatial-stage node that covers the leaf
+ * Two launches on `stream`, no host synchronisation.  All argument checks run before any device call.  (Added under ABI v8.)
+ */
+int sttm_quadtree_token_map(int T, int H, int W, int C_feat, int dtype_feat, int root_level,
+                            void* workspace, size_t workspace_bytes,
+                            int32_t* token_to_out, int32_t* token_to_node, void* stream);
+
+/*
  * Label propagation on an explicit edge list: replaces get_merge_dst_idx_safe
  * (quadtree_temporal_merger.py:223-269).  pairs is [L, 2] int32 (dst, src); rep_out is [N] int32;
  * scratch is >= (N + L) * 4 bytes; iters_out (device int32, may be NULL) receives the iteration count.

@@ -67,6 +67,7 @@ SIGNATURES = {
     "sttm_octree_build": (_i, [_vp, _i, _i, _i, _i, ctypes.c_float, _i, _vp, _sz, _vp, _vp, _vp]),
     "sttm_resize_nearest": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sttm_pack_merged_batch": (_i, [_i, _i, _i, _vp, _i64, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _i64, _i64, _vp, _vp]),
+    "sttm_quadtree_token_map": (_i, [_i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
 }
 
 

@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libsttm_hip.so")
 SOURCES = ["quadtree_spatial.hip", "spatial_f32.hip", "spatial_bf16.hip", "spatial_f16.hip", "spatial_f32_head.hip",
            "spatial_bf16_head.hip", "spatial_f16_head.hip", "spatial_pooled_f32.hip", "spatial_pooled_bf16.hip", "spatial_pooled_f16.hip",
            "spatial_col_f32.hip", "spatial_col_bf16.hip", "spatial_col_f16.hip", "spatial_wide_f32.hip", "spatial_wide_bf16.hip", "spatial_wide_f16.hip",
-           "spatial_wide_f32_head.hip", "spatial_wide_bf16_head.hip", "spatial_wide_f16_head.hip", "temporal_merge.hip", "tome.hip", "tome_snippet.hip", "pool2d.hip", "pack.hip", "dycoke.hip", "dycoke_decode.hip", "octree.hip", "api.hip"]
+           "spatial_wide_f32_head.hip", "spatial_wide_bf16_head.hip", "spatial_wide_f16_head.hip", "temporal_merge.hip", "tome.hip", "tome_snippet.hip", "pool2d.hip", "pack.hip", "token_map.hip", "dycoke.hip", "dycoke_decode.hip", "octree.hip", "api.hip"]
 HEADERS = ["sttm_common.h", "sttm_kernels.h", "tome_device.h", "sttm_pairs.inc", "quadtree_spatial.inc", "spatial_pooled.inc", "spatial_col.inc", "spatial_wide.inc", os.path.join("..", "..", "include", "sttm_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 if os.environ.get("STTM_NT_STREAM") == "1":

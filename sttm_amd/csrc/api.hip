@@ -917,6 +917,26 @@ int sttm_quadtree_apply(const void* v, int64_t stride_t, int64_t stride_c, int64
     return STTM_OK;
 }
 
+int sttm_quadtree_token_map(int T, int H, int W, int C_feat, int dtype_feat, int root_level, void* workspace, size_t workspace_bytes,
+                            int32_t* token_to_out, int32_t* token_to_node, void* stream_) {
+    if (!workspace || !token_to_out) return fail(STTM_ERR_ARG, "token map: null pointer argument");
+    if (dtype_feat < 0 || dtype_feat > 2) return fail(STTM_ERR_ARG, "token map: unknown dtype code %d", dtype_feat);
+    if (T < 1 || C_feat < 1) return fail(STTM_ERR_ARG, "token map: T and C_feat must be positive");
+    if (H > 255 || W > 255) return fail(STTM_ERR_UNSUPPORTED, "token grids larger than 255 per side are not supported");
+    if ((int64_t)T * H * W >= (1ll << 31) / 16) return fail(STTM_ERR_UNSUPPORTED, "too many tokens");
+    Plan p;
+    const int D = make_plan(T, H, W, C_feat, dtype_feat, root_level, &p);
+    if (D < 0) return D;
+    if (workspace_bytes < p.bytes) return fail(STTM_ERR_ARG, "workspace too small: %zu < %zu", workspace_bytes, p.bytes);
+    if (reinterpret_cast<uintptr_t>(workspace) % 256) return fail(STTM_ERR_ARG, "workspace must be 256-byte aligned");
+    Buffers b;
+    carve_all(p, T, H, W, C_feat, dtype_feat, reinterpret_cast<char*>(workspace), &b);
+    const hipError_t e = sttm::launch_token_map(b.meta, b.lab_row, b.gcnt, b.frame_cnt, T, H, W, token_to_out, token_to_node,
+                                                reinterpret_cast<hipStream_t>(stream_));
+    if (e != hipSuccess) return fail(STTM_ERR_LAUNCH, "token-map kernels: %s", hipGetErrorString(e));
+    return STTM_OK;
+}
+
 // The wait for N': a short busy spin (the counts usually arrive within tens of microseconds), then a yielding poll so that
 // a long kernel queue ahead of this call does not burn a core.
 int sttm_wait_counts_early(const int32_t* counts_host, const uint64_t* early_host, int n_early, int seq, int timeout_us, int32_t* out) {

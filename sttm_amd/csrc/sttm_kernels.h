@@ -256,6 +256,10 @@ struct PackArgs {
     PackRow rows[kBatchMax];
 };
 hipError_t launch_pack_merged(const PackArgs& a, int n_rows, int pack_bytes, hipStream_t stream);
+// Token map of a finished merge (token_map.hip; sttm_quadtree_token_map): two launches that turn meta / lab_row / gcnt / frame_cnt
+// into per-leaf maps
+hipError_t launch_token_map(const uint32_t* meta, const int32_t* lab_row, const int32_t* gcnt, const int32_t* frame_cnt, int T, int H, int W,
+                            int32_t* token_to_out, int32_t* token_to_node, hipStream_t stream);
 constexpr int kOctMaxLevels = 8;
 
 struct OctArgs {

@@ -272,7 +272,7 @@ def _acquire_state(dev):
 
 
 def quadtree_merge_raw(x, threshold, temporal_thresh, root_level, weighted_avg, head_dim, slow_ver=False, return_ctx=False,
-                       feat_dest=None, events=None, side_tensors=None, side_sum_mode=False, want_idx=False):
+                       feat_dest=None, events=None, side_tensors=None, side_sum_mode=False, want_idx=False, want_map=False):
     """Launch the merge of one video and return the worst-case-sized outputs plus the host counts (only the slots CNT_OUT and
     CNT_OVERFLOW are filled in on the host; the diagnostic counters stay in the device `counts` tensor of the returned context
     and are complete once the stream has drained).
@@ -283,7 +283,11 @@ def quadtree_merge_raw(x, threshold, temporal_thresh, root_level, weighted_avg, 
     ran last on this stream with this workspace", so no other host thread on the stream may get in between.  Their pooled
     [T*H*W, Cv] outputs (rows [0, N') valid) are appended to the result as a list.
     want_idx: also return the merged tokens' 1-d indices t*H*W + y1*W + x1 (int32 [T*H*W], rows [0, N') valid), written by the
-    group-mean kernel -- appended last.
+    group-mean kernel -- appended after the side tensors.
+    want_map: also return (token_to_out, token_to_node), two [T, H, W] int32 tensors: the row of the merged features every input
+    token went into, and the origin row t*H*W + y1*W + x1 of the spatial-stage node that covers it (sttm_quadtree_token_map: two
+    small launches that read this merge's tables, inside the same critical section as the side tensors) -- appended last.  Without
+    it no extra launch is issued.
 
     Host path (round 3): the device chain of one call is ~80 us and the next call cannot be issued before this one knows N', so
     every microsecond between "N' arrived" and "next spatial kernel submitted" is device idle time.  Hence: no device context
@@ -302,13 +306,13 @@ def quadtree_merge_raw(x, threshold, temporal_thresh, root_level, weighted_avg, 
     if idx is None or torch.cuda.current_device() != idx:
         with torch.cuda.device(dev):
             return _merge_on_current_device(x, dtype, threshold, temporal_thresh, root_level, weighted_avg, head_dim, slow_ver,
-                                            return_ctx, feat_dest, events, side_tensors, side_sum_mode, want_idx)
+                                            return_ctx, feat_dest, events, side_tensors, side_sum_mode, want_idx, want_map)
     return _merge_on_current_device(x, dtype, threshold, temporal_thresh, root_level, weighted_avg, head_dim, slow_ver,
-                                    return_ctx, feat_dest, events, side_tensors, side_sum_mode, want_idx)
+                                    return_ctx, feat_dest, events, side_tensors, side_sum_mode, want_idx, want_map)
 
 
 def _merge_on_current_device(x, dtype, threshold, temporal_thresh, root_level, weighted_avg, head_dim, slow_ver, return_ctx,
-                             feat_dest, events, side_tensors, side_sum_mode, want_idx=False):
+                             feat_dest, events, side_tensors, side_sum_mode, want_idx=False, want_map=False):
     st = _acquire_state(x.device)
     try:
         out = _with_barrier_retry(st, lambda flags: _merge_locked(st, x, dtype, threshold, temporal_thresh, root_level, weighted_avg,
@@ -318,6 +322,8 @@ def _merge_on_current_device(x, dtype, threshold, temporal_thresh, root_level, w
         sides = None
         if side_tensors is not None:
             sides = [_apply_side_tensor(v, ctx, root_level, side_sum_mode) for v in side_tensors]
+        # (after _with_barrier_retry: the tables are those of the call that succeeded)
+        maps = _token_map(ctx, root_level) if want_map else None
     finally:
         st.lock.release()
     res = (feat, npatch, tlbr, cnt)
@@ -327,6 +333,8 @@ def _merge_on_current_device(x, dtype, threshold, temporal_thresh, root_level, w
         res += (sides,)
     if want_idx:
         res += (idx1d,)
+    if want_map:
+        res += (maps,)
     return res
 
 
@@ -418,6 +426,17 @@ def _apply_side_tensor(v, ctx, root_level, sum_mode):
                                  ws.data_ptr(), ws.numel(), counts.data_ptr(), out.data_ptr(), stream.cuda_stream)
     _lib.raise_for(rc)
     return out
+
+
+def _token_map(ctx, root_level):
+    """(token_to_out, token_to_node) [T, H, W] int32 of the merge that just ran on the context's stream and workspace."""
+    x, ws, counts, dtype_feat, stream = ctx
+    T, C, H, W = x.shape
+    maps = torch.empty((2, T, H, W), dtype=torch.int32, device=x.device)
+    rc = _lib.load().sttm_quadtree_token_map(T, H, W, C, dtype_feat, int(root_level), ws.data_ptr(), ws.numel(),
+                                             maps[0].data_ptr(), maps[1].data_ptr(), stream.cuda_stream)
+    _lib.raise_for(rc)
+    return maps[0], maps[1]
 
 
 def get_quadtree_features_batch(videos, threshold, temporal_thresh=-1.0, root_level=0, weighted_avg=False,
@@ -672,7 +691,11 @@ def get_quadtree_features(_video_feature, threshold, temporal_thresh=-1.0, root_
     input's device; rows are ordered by (t, y1, x1) like the reference's output.
     """
     if vis_flag:
-        raise NotImplementedError("vis_flag=True (quadtree_builder_vis) is a plotting aid and is out of scope")
+        # the reference's dispatcher (quadtree_interface.py:7-9) passes only weighted_avg on: slow_ver, head_dim and the position
+        # embeddings are ignored on this path
+        assert temporal_thresh > 0, "Visualization only suppports spatio-temporal merging version"    # quadtree_builder_vis.py:13
+        feat, npatch, tlbr, t2o, t2n = get_quadtree_features_with_map(_video_feature, threshold, temporal_thresh, root_level, weighted_avg)
+        return feat, npatch, tlbr, node_metadata_from_maps(t2o, t2n)
     if pos_embs is None:
         feat, npatch, tlbr, cnt = quadtree_merge_raw(_video_feature, threshold, temporal_thresh, root_level,
                                                      weighted_avg, head_dim, slow_ver)
@@ -693,6 +716,73 @@ def get_quadtree_features(_video_feature, threshold, temporal_thresh=-1.0, root_
     else:
         out_cos, out_sin = out_cos[:n], out_sin[:n]
     return _sized(feat, npatch, tlbr, n) + ((out_cos, out_sin),)
+
+
+def get_quadtree_features_with_map(_video_feature, threshold, temporal_thresh=-1.0, root_level=0, weighted_avg=False,
+                                   slow_ver=False, head_dim=None):
+    """get_quadtree_features plus the maps that say which input token went where: returns (features, num_patches, tlbr,
+    token_to_out, token_to_node).  token_to_out [T, H, W] int32 is the row of `features` every token of the [T, H, W] grid was
+    merged into (`bincount(token_to_out) == num_patches`); token_to_node [T, H, W] int32 is the origin row t*H*W + y1*W + x1 of
+    the spatial-stage node that covers the token (before the temporal stage).  With temporal_thresh <= 0 every node is its own
+    group.  The first three results are the bits get_quadtree_features returns."""
+    feat, npatch, tlbr, cnt, (t2o, t2n) = quadtree_merge_raw(_video_feature, threshold, temporal_thresh, root_level, weighted_avg,
+                                                             head_dim, slow_ver, want_map=True)
+    return _sized(feat, npatch, tlbr, cnt[_lib.CNT_OUT]) + (t2o, t2n)
+
+
+def unmerge_tokens(features, token_to_out, out=None):
+    """Scatter merged rows back onto the token grid: out[t, y, x, :] = features[token_to_out[t, y, x], :].  features [N', C] (merged
+    features, per-token LLM outputs, attention rows ...), token_to_out [T, H, W] int32 from get_quadtree_features_with_map, every
+    entry in [0, N').  Returns [T, H, W, C] in the dtype of `features`; `out=` takes a contiguous tensor of that shape and dtype.
+    This is torch.index_select on the current stream (plus the int64 copy of the map it needs), bytes copied, not converted: the
+    library has no gather kernel of its own for it."""
+    if not (features.is_cuda and token_to_out.is_cuda):
+        raise RuntimeError("sttm_amd runs on the GPU only: features and token_to_out must be CUDA (ROCm) tensors; "
+                           "there is no CPU fallback")
+    if features.dtype not in _DTYPE_CODE:
+        raise NotImplementedError(f"dtype {features.dtype} is not supported (float32, bfloat16, float16)")
+    if features.dim() != 2 or token_to_out.dim() != 3 or token_to_out.dtype != torch.int32:
+        raise ValueError("expected features [N', C] and token_to_out [T, H, W] int32")
+    dev = features.device
+    if token_to_out.device != dev:
+        raise ValueError("features and token_to_out must be on one device")
+    shape = tuple(token_to_out.shape) + (features.shape[1],)
+    if out is None:
+        out = torch.empty(shape, dtype=features.dtype, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != features.dtype or out.device != dev or not out.is_contiguous():
+        raise ValueError(f"out= must be a contiguous {shape} tensor of the dtype and device of features")
+    torch.index_select(features, 0, token_to_out.reshape(-1).long(), out=out.view(-1, shape[-1]))
+    return out
+
+
+def node_metadata_from_maps(token_to_out, token_to_node):
+    """The `node_metadata` of the reference's vis_flag=True path (cross_frame_node_merging_vis, quadtree_temporal_merger.py:312-318)
+    from the two maps: {representative node id: [[t, y1, x1, y2, x2] of every member node]}.  A node's id is the rank of its
+    origin row among all origin rows (the reference's index into its (t, y1, x1)-sorted node list); its box is its origin and
+    max y + 1 / max x + 1 over the leaves that carry it; a group's key is its smallest node id.  Keys ascend, members ascend by
+    node id.  Host code by nature (it ends in a Python dict); tensors on any device: one transfer of the two maps, then torch ops."""
+    T, H, W = token_to_out.shape
+    t2o, t2n = torch.stack([token_to_out.reshape(-1), token_to_node.reshape(-1)]).cpu().long()          # the one transfer
+    origins, node_of_leaf = torch.unique(t2n, sorted=True, return_inverse=True)
+    n_nodes = origins.numel()
+    leaf = torch.arange(T * H * W, device=t2n.device)
+    p = leaf % (H * W)
+    zeros = torch.zeros(n_nodes, dtype=torch.long, device=t2n.device)
+    y2 = zeros.scatter_reduce(0, node_of_leaf, p // W + 1, reduce="amax", include_self=False)
+    x2 = zeros.scatter_reduce(0, node_of_leaf, p % W + 1, reduce="amax", include_self=False)
+    po = origins % (H * W)
+    boxes = torch.stack([origins // (H * W), po // W, po % W, y2, x2], dim=1)
+    out_of_node = t2o[origins]                       # a node's origin leaf carries the node's output row
+    order = torch.sort(out_of_node, stable=True).indices          # by group, members in ascending node id
+    _, counts = torch.unique_consecutive(out_of_node[order], return_counts=True)
+    flat = torch.cat([counts, order, boxes[order].reshape(-1)]).tolist()
+    G = counts.numel()
+    counts, ids, rows = flat[:G], flat[G:G + n_nodes], flat[G + n_nodes:]
+    meta, k = {}, 0
+    for c in counts:
+        meta[ids[k]] = [rows[5 * j:5 * j + 5] for j in range(k, k + c)]
+        k += c
+    return dict(sorted(meta.items()))
 
 
 def get_quadtree_features_into(dest, _video_feature, threshold, temporal_thresh=-1.0, root_level=0, weighted_avg=False,
