@@ -225,7 +225,7 @@ int tome_split_mode();       // 0 = fp32-input MFMA match kernel; > 0 = fp16 two
 // Per-frame / per-snippet ToMe (tome_snippet.hip): workspace layout of one iteration over n_seg segments of n tokens, and its launches
 struct TomeSegPlan {
     int na, nb, D, Dp;
-    size_t off_a, off_b, off_best, off_order, off_off, off_lists, total;
+    size_t off_a, off_b, off_best, off_order, off_off, off_lists, off_bflag, total;
 };
 int tome_segments_plan(int n_seg, int n, int C, int n_head, TomeSegPlan* p);      // STTM_OK, STTM_ERR_ARG or STTM_ERR_UNSUPPORTED (beyond the cap)
 hipError_t launch_tome_segments(const void* x, const float* size, const int64_t* idx, int n_seg, int n, int C, int n_head, int r, int dtype,

@@ -15,12 +15,17 @@
 
 namespace sttm {
 
+// b-row j of this clip has a non-finite unit row (some lane saw such an element): keep the smallest such j in the workspace's poison word
+__device__ __forceinline__ void tome_note_poisoned(unsigned* poison, int j, bool bad) {
+    if (__builtin_amdgcn_ballot_w64(bad) != 0ull && (threadIdx.x & 63) == 0) atomicMax(poison, 0xffffffffu - (unsigned)j);
+}
+
 // ---------------------------------------------------------------------------------------------------
 // normalise: m = mean over heads of x.reshape(n, n_head, D); m /= |m| ; a = m[0::2], b = m[1::2]
 // one wave per token row
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_tome_normalize(const float* __restrict__ x, int n, int C, int n_head, int D, int Dp,
-                                                        float* __restrict__ ahat, float* __restrict__ bhat) {
+                                                        float* __restrict__ ahat, float* __restrict__ bhat, unsigned* __restrict__ poison) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
     for (int row = blockIdx.x * nwave + wave; row < n; row += gridDim.x * nwave) {
         const float* xr = x + (int64_t)row * C;
@@ -42,6 +47,11 @@ __global__ void __launch_bounds__(256) k_tome_normalize(const float* __restrict_
         const float nrm = sqrtf(ss);
         for (int d = lane; d < D; d += 64) out[d] = out[d] / nrm;
         for (int d = D + lane; d < Dp; d += 64) out[d] = 0.f;
+        if ((row & 1) && tome_norm_degenerate(nrm)) {             // a b-row whose unit row may be non-finite (tome_device.h)
+            bool bad = false;
+            for (int d = lane; d < D; d += 64) bad |= tome_unit_nonfinite(out[d], nrm);
+            tome_note_poisoned(poison, row >> 1, bad);
+        }
     }
 }
 
@@ -319,7 +329,7 @@ __global__ void __launch_bounds__(256, 2) k_tome_match(const float* __restrict__
 // in registers between the two passes (D <= 4096).  VEC = 1: any shape.
 template <typename T, int VEC>
 __global__ void __launch_bounds__(256) k_tome_normalize16(const void* __restrict__ x, int n, int C, int n_head, int D, int Dp,
-                                                          uint16_t* __restrict__ ahat, uint16_t* __restrict__ bhat) {
+                                                          uint16_t* __restrict__ ahat, uint16_t* __restrict__ bhat, unsigned* __restrict__ poison) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
     for (int row = blockIdx.x * nwave + wave; row < n; row += gridDim.x * nwave) {
         uint16_t* out = ((row & 1) ? bhat : ahat) + (int64_t)(row >> 1) * Dp;
@@ -348,6 +358,17 @@ __global__ void __launch_bounds__(256) k_tome_normalize16(const void* __restrict
                     store_pack<T, 8>(out, d, o);
                 }
             }
+            if ((row & 1) && tome_norm_degenerate(nrm)) {         // a b-row whose unit row may be non-finite (tome_device.h)
+                bool bad = false;
+#pragma unroll
+                for (int i = 0; i < MAXCH; ++i) {
+                    if ((i * 64 + lane) * 8 < D) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) bad |= tome_unit_nonfinite(v[i].get(e), nrm);
+                    }
+                }
+                tome_note_poisoned(poison, row >> 1, bad);
+            }
         } else {
             float ss = 0.f;
             for (int d = lane; d < D; d += 64) {
@@ -365,6 +386,11 @@ __global__ void __launch_bounds__(256) k_tome_normalize16(const void* __restrict
             ss = wave_sum(ss);
             const float nrm = tome_round<T>(sqrtf(ss));
             for (int d = lane; d < D; d += 64) tome_st<T>(out, d, tome_ld<T>(out, d) / nrm);
+            if ((row & 1) && tome_norm_degenerate(nrm)) {
+                bool bad = false;
+                for (int d = lane; d < D; d += 64) bad |= tome_unit_nonfinite(tome_ld<T>(out, d), nrm);
+                tome_note_poisoned(poison, row >> 1, bad);
+            }
         }
         for (int d = D + lane; d < Dp; d += 64) out[d] = 0;
     }
@@ -506,7 +532,8 @@ __global__ void __launch_bounds__(256, 2) k_tome_match16(const uint16_t* __restr
 template <int VEC>
 __global__ void __launch_bounds__(256) k_tome_normalize_split(const float* __restrict__ x, int n, int C, int n_head, int D, int Dp,
                                                               uint16_t* __restrict__ aplanes /*[2][na][Dp]*/, int na,
-                                                              uint16_t* __restrict__ bplanes /*[2][nb][Dp]*/, int nb) {
+                                                              uint16_t* __restrict__ bplanes /*[2][nb][Dp]*/, int nb,
+                                                              unsigned* __restrict__ poison) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
     for (int row = blockIdx.x * nwave + wave; row < n; row += gridDim.x * nwave) {
         const float* xr = x + (int64_t)row * C;
@@ -537,6 +564,14 @@ __global__ void __launch_bounds__(256) k_tome_normalize_split(const float* __res
                 *reinterpret_cast<uint2*>(hi + d) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
                 *reinterpret_cast<uint2*>(lo + d) = make_uint2((uint32_t)l[0] | ((uint32_t)l[1] << 16), (uint32_t)l[2] | ((uint32_t)l[3] << 16));
             }
+            if (odd && tome_norm_degenerate(nrm)) {               // a b-row whose unit row may be non-finite (tome_device.h)
+                bool bad = false;
+                for (int d = lane * 4; d < D; d += 256) {
+                    const float4 m = *reinterpret_cast<const float4*>(xr + d);
+                    bad |= tome_unit_nonfinite(m.x, nrm) || tome_unit_nonfinite(m.y, nrm) || tome_unit_nonfinite(m.z, nrm) || tome_unit_nonfinite(m.w, nrm);
+                }
+                tome_note_poisoned(poison, row >> 1, bad);
+            }
         } else {
             auto metric = [&](int d) {
                 if (n_head == 1) return xr[d];
@@ -549,6 +584,11 @@ __global__ void __launch_bounds__(256) k_tome_normalize_split(const float* __res
             ss = wave_sum(ss);
             const float nrm = sqrtf(ss);
             for (int d = lane; d < D; d += 64) split(metric(d), nrm, hi[d], lo[d]);
+            if (odd && tome_norm_degenerate(nrm)) {
+                bool bad = false;
+                for (int d = lane; d < D; d += 64) bad |= tome_unit_nonfinite(metric(d), nrm);
+                tome_note_poisoned(poison, row >> 1, bad);
+            }
         }
         for (int d = D + lane; d < Dp; d += 64) { hi[d] = 0; lo[d] = 0; }
     }
@@ -962,7 +1002,7 @@ constexpr int kRankParts = 32;         // most key-range parts per a-block (part
 __global__ void __launch_bounds__(RK_I) k_tome_rank(const unsigned long long* __restrict__ best, int na, int jsplit, int r,
                                                     int* __restrict__ rank, int* __restrict__ arrive, float* __restrict__ node_max,
                                                     int* __restrict__ node_idx, int* __restrict__ order, int* __restrict__ cnt,
-                                                    int nb, int* __restrict__ off) {
+                                                    int nb, int* __restrict__ off, const unsigned* __restrict__ poison) {
     __shared__ __attribute__((aligned(16))) unsigned tile[RK_I];
     __shared__ int last_sh, all_sh;
     __shared__ int wsum[RK_I / 64];
@@ -970,7 +1010,8 @@ __global__ void __launch_bounds__(RK_I) k_tome_rank(const unsigned long long* __
     const int ib = blockIdx.x / jsplit, js = blockIdx.x - ib * jsplit;
     const int tid = threadIdx.x;
     const int i = ib * RK_I + tid;
-    const unsigned long long bi = i < na ? best[i] : 0ull;
+    const unsigned pw = *poison;            // 0xffffffff - (the first poisoned b-row), 0 on clean inputs (tome_device.h)
+    const unsigned long long bi = i < na ? tome_poisoned_best(best[i], pw) : 0ull;
     const unsigned long long ki = tome_rank_key(bi, i);
     const int chunk = ((na + jsplit - 1) / jsplit + RK_I - 1) / RK_I * RK_I;
     const int jlo = js * chunk, jhi = min(na, jlo + chunk);
@@ -983,7 +1024,7 @@ __global__ void __launch_bounds__(RK_I) k_tome_rank(const unsigned long long* __
     int c = 0;
     for (int j0 = jlo; j0 < jhi; j0 += RK_I) {       // one aligned block of 256 keys per step
         const int jj = j0 + tid;
-        tile[tid] = jj < jhi ? (unsigned)(tome_rank_key(best[jj], jj) >> 32) : 0u;      // 0 is below every key
+        tile[tid] = jj < jhi ? (unsigned)(tome_rank_key(tome_poisoned_best(best[jj], pw), jj) >> 32) : 0u;      // 0 is below every key
         __syncthreads();
         const int nq = min(RK_I, jhi - j0);
         if (j0 == ib * RK_I) {                       // the diagonal block
@@ -1242,7 +1283,7 @@ __global__ void __launch_bounds__(256) k_tome_merge(const void* __restrict__ x, 
 
 struct TomePlan {
     int na, nb, D, Dp;
-    size_t off_ahat, off_bhat, off_best, off_nmax, off_nidx, off_order, off_cnt, off_cur, off_rank, off_arrive, off_off, off_parts, off_lists, total;
+    size_t off_ahat, off_bhat, off_best, off_nmax, off_nidx, off_order, off_cnt, off_cur, off_poison, off_arrive, off_off, off_parts, off_lists, total;
 };
 
 static int tome_cu_count() {
@@ -1271,12 +1312,12 @@ static int tome_plan(int n, int C, int n_head, TomePlan* p) {
     p->off_nmax = o; o = al(o + (size_t)p->na * 4);
     p->off_nidx = o; o = al(o + (size_t)p->na * 4);
     p->off_order = o; o = al(o + (size_t)p->na * 4);
-    // ONE zeroed region [off_best, off_off): the packed best scores, the per-destination counts and cursors, the partial ranks and
+    // ONE zeroed region [off_best, off_off): the packed best scores, the per-destination counts and cursors, the poison word and
     // the per-block arrival counters of the ranking kernel
     p->off_best = o; o = al(o + (size_t)p->na * 8);
     p->off_cnt = o; o = al(o + (size_t)(p->nb + 1) * 4);
     p->off_cur = o; o = al(o + (size_t)(p->nb + 1) * 4);
-    p->off_rank = o; o = al(o + (size_t)p->na * 4);               // (not part of the zeroed region any more: see off_parts)
+    p->off_poison = o; o = al(o + 4);                             // the poison word (tome_device.h); must stay inside the zeroed region
     p->off_arrive = o; o = al(o + (size_t)((p->na + RK_I - 1) / RK_I + 1) * 4);
     p->off_off = o; o = al(o + (size_t)(p->nb + 2) * 4);
     p->off_lists = o; o = al(o + (size_t)p->na * 4);
@@ -1320,7 +1361,8 @@ int sttm_tome_step(const void* x_, const float* size, const int64_t* idx, int n,
 
     int* rank = reinterpret_cast<int*>(ws + p.off_parts);
     int* arrive = reinterpret_cast<int*>(ws + p.off_arrive);
-    (void)hipMemsetAsync(best, 0, p.off_off - p.off_best, stream);     // best, cnt, cur, rank, arrive: one contiguous region
+    unsigned* poison = reinterpret_cast<unsigned*>(ws + p.off_poison);
+    (void)hipMemsetAsync(best, 0, p.off_off - p.off_best, stream);     // best, cnt, cur, poison, arrive: one contiguous region
     const int ngrid = [&] { int g = (n + 3) / 4; return g > 8192 ? 8192 : g; }();
     // j-split: the grid is itiles*jsplit workgroups of ceil(jtiles/jsplit) tile products each, `resident` per CU.
     // Pick the split with the smallest per-CU critical path  ceil(WGs / slots) * tiles-per-WG  (a 588-WG grid on 512
@@ -1362,10 +1404,10 @@ int sttm_tome_step(const void* x_, const float* size, const int64_t* idx, int n,
         uint16_t* bp = reinterpret_cast<uint16_t*>(bhat);
         if (n_head == 1 && C % 4 == 0 && reinterpret_cast<uintptr_t>(x_) % 16 == 0)
             hipLaunchKernelGGL(k_tome_normalize_split<4>, dim3(ngrid), dim3(256), 0, stream, reinterpret_cast<const float*>(x_), n, C,
-                               n_head, p.D, p.Dp, ap, p.na, bp, p.nb);
+                               n_head, p.D, p.Dp, ap, p.na, bp, p.nb, poison);
         else
             hipLaunchKernelGGL(k_tome_normalize_split<1>, dim3(ngrid), dim3(256), 0, stream, reinterpret_cast<const float*>(x_), n, C,
-                               n_head, p.D, p.Dp, ap, p.na, bp, p.nb);
+                               n_head, p.D, p.Dp, ap, p.na, bp, p.nb, poison);
         // tome_split: 1 = four product terms, 2 = three (without l.l); 3/4 force the 128-tile / the 256-tile DMA kernel (4 terms),
         // 5/6 the same with 3 terms.  The 256-tile kernel wins from ~6 k tokens on (measured cross-over: T = 32 frames of 196).
         // 7 = the four-wave form of the 256-tile kernel (128 x 128 wave tiles, round 6), 3 terms
@@ -1396,7 +1438,7 @@ int sttm_tome_step(const void* x_, const float* size, const int64_t* idx, int n,
             else hipLaunchKernelGGL((k_tome_match_split<TM_K, 2, 2, 3>), dim3(itiles * jsplit), dim3(256), lds, stream, ap, bp, p.na, p.nb, p.Dp, jsplit, best);
         }
     } else if (dtype == STTM_F32) {
-        hipLaunchKernelGGL(k_tome_normalize, dim3(ngrid), dim3(256), 0, stream, reinterpret_cast<const float*>(x_), n, C, n_head, p.D, p.Dp, ahat, bhat);
+        hipLaunchKernelGGL(k_tome_normalize, dim3(ngrid), dim3(256), 0, stream, reinterpret_cast<const float*>(x_), n, C, n_head, p.D, p.Dp, ahat, bhat, poison);
         hipLaunchKernelGGL(k_tome_match, dim3(itiles * jsplit), dim3(256), 0, stream, ahat, bhat, p.na, p.nb, p.Dp, jsplit, best);
     } else {
         // 16-bit inputs: the 256-tile DMA kernel from ~6 k tokens on ("tome_split" 3 / 5 force the 128-tile kernel, 4 / 6 the
@@ -1416,9 +1458,9 @@ int sttm_tome_step(const void* x_, const float* size, const int64_t* idx, int n,
 #define STTM_TOME_16(TT)                                                                                                            \
         do {                                                                                                                        \
             if (n_head == 1 && C % 8 == 0 && C <= 4096 && reinterpret_cast<uintptr_t>(x_) % 16 == 0)                              \
-                hipLaunchKernelGGL((k_tome_normalize16<TT, 8>), dim3(ngrid), dim3(256), 0, stream, x_, n, C, n_head, p.D, p.Dp, ap, bp); \
+                hipLaunchKernelGGL((k_tome_normalize16<TT, 8>), dim3(ngrid), dim3(256), 0, stream, x_, n, C, n_head, p.D, p.Dp, ap, bp, poison); \
             else                                                                                                                    \
-                hipLaunchKernelGGL((k_tome_normalize16<TT, 1>), dim3(ngrid), dim3(256), 0, stream, x_, n, C, n_head, p.D, p.Dp, ap, bp); \
+                hipLaunchKernelGGL((k_tome_normalize16<TT, 1>), dim3(ngrid), dim3(256), 0, stream, x_, n, C, n_head, p.D, p.Dp, ap, bp, poison); \
             if (big && abl16 == 3) hipLaunchKernelGGL((k_tome_match_glds<1, 1, TT, ABL16A>), dim3(js ? it * js : it), dim3(512), 2 * TG_BUF, stream, ap, bp, p.na, p.nb, p.Dp, js, best); \
             else if (big && abl16 == 4) hipLaunchKernelGGL((k_tome_match_glds<1, 1, TT, ABL16B>), dim3(js ? it * js : it), dim3(512), 2 * TG_BUF, stream, ap, bp, p.na, p.nb, p.Dp, js, best); \
             else if (big && abl16 == 5) hipLaunchKernelGGL((k_tome_match_glds<1, 1, TT, ABL16C>), dim3(js ? it * js : it), dim3(512), 2 * TG_BUF, stream, ap, bp, p.na, p.nb, p.Dp, js, best); \
@@ -1443,7 +1485,7 @@ int sttm_tome_step(const void* x_, const float* size, const int64_t* idx, int n,
         if (js > max_js) js = max_js;
         if (js > kRankParts) js = kRankParts;
         if (js < 1) js = 1;
-        hipLaunchKernelGGL(k_tome_rank, dim3(iblocks * js), dim3(RK_I), 0, stream, best, p.na, js, r, rank, arrive, nmax, nidx, order, cnt, p.nb, off);
+        hipLaunchKernelGGL(k_tome_rank, dim3(iblocks * js), dim3(RK_I), 0, stream, best, p.na, js, r, rank, arrive, nmax, nidx, order, cnt, p.nb, off, poison);
         hipLaunchKernelGGL(k_tome_fill, dim3((r + 255) / 256), dim3(256), 0, stream, order, nidx, r, off, cur, lists);
     }
     {

@@ -100,6 +100,28 @@ __device__ __forceinline__ unsigned long long tome_rank_key(unsigned long long b
     return ((unsigned long long)ku << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
 }
 
+// Poisoned b-rows.  The reference divides by the norm without an eps, so a token with a NaN, an Inf (inf / inf) or nothing but zeros
+// (0 / 0) has a unit row that holds a NaN, and a token whose sum of squares underflows (norm 0) has a unit row of +-Inf.  EVERY score
+// against such a row is NaN -- NaN products, or infinities of both signs in one sum -- and torch.max propagates NaN and returns the
+// first NaN's index: with such a b-row j* every a-row's (node_max, node_idx) is (NaN, j*) -- (NaN, 0) for an a-row that is poisoned
+// itself, whose scores are all NaN.  The running maxima of the match kernels skip NaN scores (a compare with NaN is false), which is
+// right for the poisoned a-row (no score wins: its packed best stays 0 = a NaN row with index 0) and wrong for a clean a-row facing j*.
+// The match kernels stay as they are: the normalise kernels, which visit every unit row anyway, note the smallest b-row with a
+// non-finite unit row (`poison` word: 0xffffffff - j* by atomicMax, 0 = none; per segment a flag per b-row in tome_snippet.hip), and
+// the ranking kernels replace every row's packed best by (NaN, j*) when there is one.  A unit row can be non-finite only if the norm is
+// 0, Inf or NaN -- one wave-uniform compare per row on clean inputs; only then are the row's elements looked at.
+// (The one case this leaves to chance: against a +-Inf unit row of k elements an a-row whose k products all have one sign scores +-Inf
+// in the reference, not NaN -- 2^-(k-1) of the a-rows, k = the metric width)
+__device__ __forceinline__ bool tome_norm_degenerate(float nrm) { return !(nrm > 0.f && nrm < INFINITY); }
+// with a degenerate norm: is elem / nrm non-finite?  norm 0 or NaN: always (+-Inf, 0 / 0 or NaN); norm Inf: iff elem is +-Inf or NaN.
+// (Also right for an element that is already divided: then it is 0 or NaN under an Inf norm.)
+__device__ __forceinline__ bool tome_unit_nonfinite(float elem, float nrm) { return !(nrm == INFINITY) || !(fabsf(elem) < INFINITY); }
+__device__ __forceinline__ unsigned long long tome_poisoned_best(unsigned long long b, unsigned pw) {
+    // pw = 0xffffffff - j*, which is pack_score's low word of candidate j*; 0xffc00000 = pack_score's high word of the quiet NaN.
+    // b == 0 (no score of the row compared true: all NaN) keeps index 0, the first NaN of such a row.
+    return (pw != 0u && b != 0ull) ? ((0xffc00000ull << 32) | (unsigned long long)pw) : b;
+}
+
 template <typename T, int VEC> __device__ __forceinline__ void tome_ld_vec(const void* x, int64_t off, float (&v)[VEC]) {
     if constexpr (VEC == 1) {
         v[0] = tome_ld<T>(x, off);

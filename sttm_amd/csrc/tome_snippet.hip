@@ -24,7 +24,7 @@ constexpr int kTsnMaxHalf = (kTsnMaxTokens + 1) / 2;       // a-rows / b-rows of
 // ---------------------------------------------------------------------------------------------------
 template <typename T, int VEC>
 __global__ void __launch_bounds__(256) k_tsn_normalize(const void* __restrict__ x_, int n_seg, int n, int C, int n_head, int D, int Dp,
-                                                       uint16_t* __restrict__ ap, uint16_t* __restrict__ bp) {
+                                                       uint16_t* __restrict__ ap, uint16_t* __restrict__ bp, int* __restrict__ bflag /*[n_seg * nb]*/) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwave = blockDim.x >> 6;
     const int na = (n + 1) / 2, nb = n / 2;
     const int total = n_seg * n;
@@ -33,6 +33,9 @@ __global__ void __launch_bounds__(256) k_tsn_normalize(const void* __restrict__ 
         const bool odd = l & 1;
         const int64_t mrow = (int64_t)seg * (odd ? nb : na) + (l >> 1);
         uint16_t* out = (odd ? bp : ap) + mrow * Dp;
+        // b-rows: is the unit row non-finite (tome_device.h: only possible with a norm of 0, Inf or NaN)?  Every b-row writes its flag,
+        // so the flags need no zeroing; k_tsn_rank takes the segment's first flagged row.
+        bool bad = false;
         if constexpr (std::is_same<T, float>::value) {
             const float* xr = reinterpret_cast<const float*>(x_) + (int64_t)row * C;
             uint16_t* hi = out;
@@ -59,6 +62,12 @@ __global__ void __launch_bounds__(256) k_tsn_normalize(const void* __restrict__ 
                     *reinterpret_cast<uint2*>(hi + d) = make_uint2((uint32_t)h[0] | ((uint32_t)h[1] << 16), (uint32_t)h[2] | ((uint32_t)h[3] << 16));
                     *reinterpret_cast<uint2*>(lo + d) = make_uint2((uint32_t)lw[0] | ((uint32_t)lw[1] << 16), (uint32_t)lw[2] | ((uint32_t)lw[3] << 16));
                 }
+                if (odd && tome_norm_degenerate(nrm)) {
+                    for (int d = lane * 4; d < D; d += 256) {
+                        const float4 m = *reinterpret_cast<const float4*>(xr + d);
+                        bad |= tome_unit_nonfinite(m.x, nrm) || tome_unit_nonfinite(m.y, nrm) || tome_unit_nonfinite(m.z, nrm) || tome_unit_nonfinite(m.w, nrm);
+                    }
+                }
             } else {
                 auto metric = [&](int d) {
                     if (n_head == 1) return xr[d];
@@ -71,6 +80,9 @@ __global__ void __launch_bounds__(256) k_tsn_normalize(const void* __restrict__ 
                 ss = wave_sum(ss);
                 const float nrm = sqrtf(ss);
                 for (int d = lane; d < D; d += 64) split(metric(d), nrm, hi[d], lo[d]);
+                if (odd && tome_norm_degenerate(nrm)) {
+                    for (int d = lane; d < D; d += 64) bad |= tome_unit_nonfinite(metric(d), nrm);
+                }
             }
             for (int d = D + lane; d < Dp; d += 64) { hi[d] = 0; lo[d] = 0; }
         } else {
@@ -99,6 +111,15 @@ __global__ void __launch_bounds__(256) k_tsn_normalize(const void* __restrict__ 
                         store_pack<T, 8>(out, d, o);
                     }
                 }
+                if (odd && tome_norm_degenerate(nrm)) {
+#pragma unroll
+                    for (int i = 0; i < MAXCH; ++i) {
+                        if ((i * 64 + lane) * 8 < D) {
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) bad |= tome_unit_nonfinite(v[i].get(e), nrm);
+                        }
+                    }
+                }
             } else {
                 float ss = 0.f;
                 for (int d = lane; d < D; d += 64) {
@@ -116,8 +137,15 @@ __global__ void __launch_bounds__(256) k_tsn_normalize(const void* __restrict__ 
                 ss = wave_sum(ss);
                 const float nrm = tome_round<T>(sqrtf(ss));
                 for (int d = lane; d < D; d += 64) tome_st<T>(out, d, tome_ld<T>(out, d) / nrm);
+                if (odd && tome_norm_degenerate(nrm)) {
+                    for (int d = lane; d < D; d += 64) bad |= tome_unit_nonfinite(tome_ld<T>(out, d), nrm);
+                }
             }
             for (int d = D + lane; d < Dp; d += 64) out[d] = 0;
+        }
+        if (odd) {
+            const bool any = __builtin_amdgcn_ballot_w64(bad) != 0ull;
+            if (lane == 0) bflag[mrow] = any ? 1 : 0;
         }
     }
 }
@@ -238,16 +266,23 @@ __global__ void __launch_bounds__(256, 2) k_tsn_match(const uint16_t* __restrict
 // (argsort(node_max, descending), ties to the smaller index); the r best a-rows are sources, grouped per destination b-row in
 // rank order:  order [n_seg][na] a-rows by rank, off [n_seg][nb + 1] list starts, lists [n_seg][na] a-rows (r entries used).
 // ---------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) k_tsn_rank(const unsigned long long* __restrict__ best, int na, int nb, int r,
+__global__ void __launch_bounds__(256) k_tsn_rank(const unsigned long long* __restrict__ best, const int* __restrict__ bflag, int na, int nb, int r,
                                                   int* __restrict__ order, int* __restrict__ off, int* __restrict__ lists) {
     __shared__ unsigned long long key[kTsnMaxHalf];
     __shared__ int ord[kTsnMaxHalf], dst[kTsnMaxHalf];
     __shared__ __attribute__((aligned(16))) int dk[kTsnMaxHalf + 4];      // destination of the source of rank k
     __shared__ int cnt[kTsnMaxHalf + 1];
+    __shared__ unsigned pw_sh;                 // 0xffffffff - (the segment's first poisoned b-row), 0 on clean inputs (tome_device.h)
     const int tid = threadIdx.x, seg = blockIdx.x;
     const int64_t a_base = (int64_t)seg * na;
+    if (tid == 0) pw_sh = 0u;
+    __syncthreads();
+    for (int j = tid; j < nb; j += 256)
+        if (bflag[(int64_t)seg * nb + j]) atomicMax(&pw_sh, 0xffffffffu - (unsigned)j);
+    __syncthreads();
+    const unsigned pw = pw_sh;
     for (int i = tid; i < na; i += 256) {
-        const unsigned long long b = best[a_base + i];
+        const unsigned long long b = tome_poisoned_best(best[a_base + i], pw);
         key[i] = tome_rank_key(b, i);
         dst[i] = b ? (int)(0xffffffffu - (unsigned)(b & 0xffffffffu)) : 0;
     }
@@ -404,6 +439,7 @@ int tome_segments_plan(int n_seg, int n, int C, int n_head, TomeSegPlan* p) {
     p->off_order = o; o = tsn_al(o + (size_t)n_seg * p->na * 4);
     p->off_off = o; o = tsn_al(o + (size_t)n_seg * (p->nb + 1) * 4);
     p->off_lists = o; o = tsn_al(o + (size_t)n_seg * p->na * 4);
+    p->off_bflag = o; o = tsn_al(o + (size_t)n_seg * (p->nb > 0 ? p->nb : 1) * 4);
     p->total = o;
     return STTM_OK;
 }
@@ -417,30 +453,31 @@ hipError_t launch_tome_segments(const void* x, const float* size, const int64_t*
     int* order = reinterpret_cast<int*>(ws + p.off_order);
     int* off = reinterpret_cast<int*>(ws + p.off_off);
     int* lists = reinterpret_cast<int*>(ws + p.off_lists);
+    int* bflag = reinterpret_cast<int*>(ws + p.off_bflag);
     const long long rows = (long long)n_seg * n;
     const int ngrid = (int)((rows + 3) / 4 > 8192 ? 8192 : (rows + 3) / 4);
     const int itiles = (p.na + TSN_T - 1) / TSN_T;
     const bool al16 = reinterpret_cast<uintptr_t>(x) % 16 == 0;
     if (dtype == STTM_F32) {
         if (n_head == 1 && C % 4 == 0 && al16)
-            hipLaunchKernelGGL((k_tsn_normalize<float, 4>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp);
+            hipLaunchKernelGGL((k_tsn_normalize<float, 4>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp, bflag);
         else
-            hipLaunchKernelGGL((k_tsn_normalize<float, 1>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp);
+            hipLaunchKernelGGL((k_tsn_normalize<float, 1>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp, bflag);
         // three plane products (without l.l), the default of the per-clip path ("tome_split" = 2)
         hipLaunchKernelGGL((k_tsn_match<f16_t, 2, 3>), dim3(n_seg * itiles), dim3(256), 0, stream, ap, bp, n_seg, p.na, p.nb, p.Dp, itiles, best);
     } else {
 #define STTM_TSN_16(TT)                                                                                                                   \
         do {                                                                                                                              \
             if (n_head == 1 && C % 8 == 0 && C <= 4096 && al16)                                                                           \
-                hipLaunchKernelGGL((k_tsn_normalize<TT, 8>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp); \
+                hipLaunchKernelGGL((k_tsn_normalize<TT, 8>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp, bflag); \
             else                                                                                                                          \
-                hipLaunchKernelGGL((k_tsn_normalize<TT, 1>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp); \
+                hipLaunchKernelGGL((k_tsn_normalize<TT, 1>), dim3(ngrid), dim3(256), 0, stream, x, n_seg, n, C, n_head, p.D, p.Dp, ap, bp, bflag); \
             hipLaunchKernelGGL((k_tsn_match<TT, 1, 1>), dim3(n_seg * itiles), dim3(256), 0, stream, ap, bp, n_seg, p.na, p.nb, p.Dp, itiles, best); \
         } while (0)
         if (dtype == STTM_BF16) STTM_TSN_16(bf16_t); else STTM_TSN_16(f16_t);
 #undef STTM_TSN_16
     }
-    hipLaunchKernelGGL(k_tsn_rank, dim3(n_seg), dim3(256), 0, stream, best, p.na, p.nb, r, order, off, lists);
+    hipLaunchKernelGGL(k_tsn_rank, dim3(n_seg), dim3(256), 0, stream, best, bflag, p.na, p.nb, r, order, off, lists);
     {
         const long long orows = (long long)n_seg * (n - r);
         const int grid = (int)((orows + 3) / 4 > 8192 ? 8192 : (orows + 3) / 4);
