@@ -16,7 +16,7 @@ The arithmetic is written out with numpy (no call into torch's pooling / interpo
       out = h0 * (w0 * x[i0, j0] + w1 * x[i0, j1]) + h1 * (w0 * x[i1, j0] + w1 * x[i1, j1])      in float32
   average (:185-186, `F.avg_pool2d(stride)`): windows of stride x stride, floor(side / stride) outputs per axis, sum in
       float32 in row-major order, divided by stride^2
-  max (:187-188, `F.max_pool2d(stride)`): same windows, maximum
+  max (:187-188, `F.max_pool2d(stride)`): same windows, maximum; a NaN in the window is returned (ATen: `(val > maxval) || isnan(val)`)
   stride == 1 (:174-175): the input is returned as is.
 """
 import math
@@ -67,7 +67,13 @@ def get_2dpool(image_feature, stride=2, height=None, width=None, mode="bilinear"
         oh, ow = height // stride, width // stride
         win = x[:, :oh * stride, :ow * stride].reshape(T, oh, stride, ow, stride, C)
         if mode == "max":
-            out = win.max(axis=(2, 4))
+            # ATen's rule, in the window's row-major order: a later value replaces the maximum when (val > max) or isnan(val) -- a
+            # NaN reaches the output, and of equal values (-0.0 / +0.0) the first one stays
+            out = np.full((T, oh, ow, C), -np.inf, dtype=np.float32)
+            for dy in range(stride):
+                for dx in range(stride):
+                    v = win[:, :, dy, :, dx]
+                    out = np.where((v > out) | np.isnan(v), v, out)
         else:
             acc = np.zeros((T, oh, ow, C), dtype=np.float32)
             for dy in range(stride):

@@ -75,7 +75,8 @@ __global__ void __launch_bounds__(512) k_pool2d(PoolArgs a) {
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {
                         const float v = p.get(e);
-                        acc[e] = is_max ? (v > acc[e] ? v : acc[e]) : acc[e] + v;
+                        // ATen's max_pool2d rule: (val > maxval) || isnan(val) -- a NaN in the window reaches the output
+                        acc[e] = is_max ? ((v > acc[e] || v != v) ? v : acc[e]) : acc[e] + v;
                     }
                 }
             Pack<T, VEC> res;

@@ -61,11 +61,12 @@ __device__ __forceinline__ Pack<T, VEC> pool_combine(int mode, const PoolTaps& t
             const pool_f2 bot = t.w0 * c + t.w1 * d;
             r = t.h0 * top + t.h1 * bot;
         } else if (mode == STTM_POOL_MAX) {
+            // k_pool2d's (= ATen's) rule: (val > maxval) || isnan(val), so a NaN in the window reaches the leaf
             pool_f2 m = {-INFINITY, -INFINITY};
-            m.x = a.x > m.x ? a.x : m.x; m.y = a.y > m.y ? a.y : m.y;
-            m.x = b.x > m.x ? b.x : m.x; m.y = b.y > m.y ? b.y : m.y;
-            m.x = c.x > m.x ? c.x : m.x; m.y = c.y > m.y ? c.y : m.y;
-            m.x = d.x > m.x ? d.x : m.x; m.y = d.y > m.y ? d.y : m.y;
+            m.x = (a.x > m.x || a.x != a.x) ? a.x : m.x; m.y = (a.y > m.y || a.y != a.y) ? a.y : m.y;
+            m.x = (b.x > m.x || b.x != b.x) ? b.x : m.x; m.y = (b.y > m.y || b.y != b.y) ? b.y : m.y;
+            m.x = (c.x > m.x || c.x != c.x) ? c.x : m.x; m.y = (c.y > m.y || c.y != c.y) ? c.y : m.y;
+            m.x = (d.x > m.x || d.x != d.x) ? d.x : m.x; m.y = (d.y > m.y || d.y != d.y) ? d.y : m.y;
             r = m;
         } else {
             const pool_f2 z = {0.f, 0.f};

@@ -55,8 +55,11 @@ def test_octree_interface_behaviour():
     out = get_octree_features(x, 2.0, 0)
     assert torch.equal(out, x.permute(0, 2, 3, 1).reshape(-1, 16))
     # threshold below every cosine: only the root cells remain
+    from oracle import octree_oracle as OC
     out = get_octree_features(x, -2.0, 0)
     assert out.shape[0] == 8
+    exp = OC.get_octree_features(x.cpu(), -2.0, 0)                        # the eight root means, in order
+    assert exp.shape[0] == 8 and float((out.cpu() - exp).abs().max()) <= 1e-5
 
 
 def test_octree_pattern_runs_on_device():
