@@ -9,12 +9,18 @@ class and overwrite its `.forward` (quadtree_attn_monkey_patch.py:177-187, tome_
 that says so.
 
 The reference pins transformers==4.45.2 and patches a verbatim copy of that version's Qwen2Model.forward.  This
-build targets the transformers that is installed (5.x decoder-layer API): the patched forward below is the
-installed `Qwen2Model.forward` with the merge step inserted before layer `sa_start_layer_idx` on prefill.
-State read by the hook is the same: `self.image_token_start_index`, `self.image_token_length`, `self.num_frame`
+build targets the transformers that is installed (5.x decoder-layer API): `_forward` below is the installed decoder forward
+with the merge step inserted before layer `sa_start_layer_idx` on prefill.  It is ONE skeleton for both model families; what
+differs between Qwen2 and the Qwen2-VL text model is the `_Family` record it is called with (`_QWEN2`, `_QWEN2VL`): position-id
+handling, the batched hook, the layer slice, what is returned as the cache, and the table `pattern -> (fires, hook)` of the
+batch-1 hooks.  Every `replace_*` goes through the one `_install`.
+State read by the hook is the same as the reference's: `self.image_token_start_index`, `self.image_token_length`, `self.num_frame`
 (0-d tensors set by generate(), llava/model/language_model/llava_qwen.py:141-143), plus `image_H/image_W` for Qwen2-VL.
 For "quadtree" they may also be 1-D tensors of length B: the batched hook of a left-padded batch ("Batched prompts").
 """
+import importlib
+from collections import namedtuple
+
 import torch
 
 from . import patch_hooks
@@ -35,7 +41,7 @@ def _is_prefill(past_key_values):
     return past_key_values is None or past_key_values.get_seq_length() == 0
 
 
-def _rebuild_masks(self, mask_map, hidden_states, past_key_values, position_ids=None):
+def _rebuild_masks(self, mask_map, hidden_states):
     """Masks for the SHORTER sequence after the merge.  The reference computes `causal_mask` once before the layer loop
     and never updates it (quadtree_attn_monkey_patch.py:60-66 vs :88-117), which only works when that mask is None
     (flash-attention / SDPA without padding).  Here the masks are rebuilt on the merged hidden states, so eager attention
@@ -152,6 +158,15 @@ def _reset_merged_mask(past_key_values):
 
 # ---- DyCoke stage 2 ("dycoke": decode-time KV selection, dycoke_attn_monkey_patch.py) -----------------------------------------
 DYCOKE_ATTN = "sttm_dycoke"           # name of the dispatching attention function in transformers' AttentionInterface
+_DECODE_FNS = ("sttm_decode_scores_fn", "sttm_decode_select_fn", "sttm_decode_attn_fn")
+_DECODE_DEFAULTS = dict(zip(_DECODE_FNS, ((".dycoke_decode", fn) for fn in ("decode_attn_scores", "select_keep", "gathered_decode_attention"))))
+
+
+def _resolve(default):
+    """An injection default: a function, or a (module, name) pair that is imported only when it is needed."""
+    if isinstance(default, tuple):
+        return getattr(importlib.import_module(default[0], __package__), default[1])
+    return default
 
 
 class _DycokeStep:
@@ -198,7 +213,7 @@ def _dycoke_step(self, inputs_embeds, past_key_values):
     if any(t != "full_attention" for t in cfg.layer_types[l - 1:]):
         raise NotImplementedError(f"a sliding-window layer at or after dycoke_l - 1 = {l - 1} is not supported by DyCoke stage 2")
     head_dim = self.layers[l].self_attn.head_dim
-    own = type(self).sttm_decode_attn_fn is _default_decode_fns()[2]
+    own = type(self).sttm_decode_attn_fn is _resolve(_DECODE_DEFAULTS["sttm_decode_attn_fn"])
     if own and head_dim not in (64, 128):
         raise NotImplementedError(f"head dimension {head_dim}: the decode kernels are built for 64 and 128")
     if own and inputs_embeds.dtype not in (torch.float32, torch.bfloat16, torch.float16):
@@ -213,35 +228,168 @@ def _dycoke_step(self, inputs_embeds, past_key_values):
     return _DycokeStep(type(self), cfg._attn_implementation, l, start, n0, num_keep)
 
 
-def _default_decode_fns():
-    from .dycoke_decode import decode_attn_scores, gathered_decode_attention, select_keep
-    return decode_attn_scores, select_keep, gathered_decode_attention
+# ---- the batch-1 hooks: fn(self, layer, hidden_states, position_ids, position_embeddings, start, length, T) ----------------------
+# -> (hidden_states, position_ids, position_embeddings or None = "compute them from the new ids", merged_token_1d_idx)
+_KEEP_IDX = object()                  # in place of an index: leave `self.merged_token_1d_idx` as it is
 
 
-def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
-                              inputs_embeds=None, use_cache=None, **kwargs):
-    """`_qwen2_forward` under the pattern's decode-time switches: a "dycoke" decode step runs with the dispatching attention function
-    and its per-forward state on the config; both are put back whatever happens."""
-    if self.sttm_pattern != "dycoke":
-        return _qwen2_forward(self, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs)
-    x = inputs_embeds if inputs_embeds is not None else input_ids
-    if x is not None and x.shape[0] != 1:
-        raise NotImplementedError(f"DyCoke reads row 0 of the attention matrix (`[0, -1]`) and prunes one video: batch size 1 only, got {x.shape[0]}")
-    cfg = self.config
-    saved = cfg._attn_implementation
-    try:
-        return _qwen2_forward(self, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs)
-    finally:
-        if cfg._attn_implementation != saved:
-            cfg._attn_implementation = saved
-        if getattr(cfg, "_sttm_dycoke_step", None) is not None:
-            cfg._sttm_dycoke_step = None
+def _head_dim(self, layer):
+    return layer.self_attn.head_dim if getattr(self, "sim_per_head", False) else None
 
 
-def _qwen2_forward(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
-                              inputs_embeds=None, use_cache=None, **kwargs):
-    """transformers 5.x Qwen2Model.forward + the STTM / ToMe hook (prefill).  "quadtree" on B > 1 left-padded prompts (or 1-D hook
-    attributes) takes the batched hook; every other case runs the batch-1 hook."""
+def _fused_merge_fn(cls):
+    """Fused slice -> merge -> concat (the kernels write the merged rows into the new hidden-state buffer) is used
+    whenever the merge function is the library's own; an injected `sttm_merge_fn` (tests) takes the plain path."""
+    return get_quadtree_features_into if cls.sttm_merge_fn is get_quadtree_features else None
+
+
+def _tome_merge_fn(cls):
+    """The merge function the ToMe hook hands to patch_hooks.tome_merge: `sttm_tome_fn(video, prune_ratio, tome_ver)` as the
+    reference dispatches it, or -- when the installer was given sa_tome_snippet_size -- per-snippet ToMe, which ignores tome_ver."""
+    size = getattr(cls, "sa_tome_snippet_size", None)
+    if size is None:
+        return cls.sttm_tome_fn
+    fn = cls.sttm_tome_snippet_fn
+    return lambda video, prune_ratio, _tome_ver: fn(video, prune_ratio, size)
+
+
+def _tree_args(self):
+    return self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg
+
+
+def _with_new_embeddings(res):
+    hidden_states, position_ids, idx = res
+    return hidden_states, position_ids, None, idx
+
+
+def _hook_quadtree(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    return _with_new_embeddings(patch_hooks.quadtree_merge_llava(
+        hidden_states, position_ids, start, length, T, type(self).sttm_merge_fn, *_tree_args(self), slow_ver=self.sttm_slow_ver,
+        head_dim=_head_dim(self, layer), merge_into_fn=_fused_merge_fn(type(self))))
+
+
+def _hook_quadtree_abl_pos(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    return patch_hooks.quadtree_merge_abl_pos(                        # this hook decides its own position embeddings
+        hidden_states, position_ids, position_embeddings, start, length, T, type(self).sttm_merge_fn, *_tree_args(self),
+        self.pos_emb_ver, self.pos_emb_weighted_avg, self.rotary_emb, slow_ver=self.sttm_slow_ver, head_dim=_head_dim(self, layer))
+
+
+def _hook_dycoke(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    return _with_new_embeddings(patch_hooks.dycoke_merge(
+        hidden_states, position_ids, start, length, T, type(self).sttm_dycoke_fn, self.sa_prune_ratio))
+
+
+def _hook_octree(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    hidden_states, position_ids = patch_hooks.octree_merge(
+        hidden_states, position_ids, start, length, T, type(self).sttm_octree_fn, self.sa_tree_thresh, self.sa_tree_root_level)
+    return hidden_states, position_ids, None, None                    # the reference's octree hook keeps no token index
+
+
+def _hook_tome(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    return _with_new_embeddings(patch_hooks.tome_merge(
+        hidden_states, position_ids, start, length, T, _tome_merge_fn(type(self)), self.sa_prune_ratio, self.sa_tome_ver))
+
+
+def _hook_pyrd(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    """Fixed-size pyramid baseline: may fire at several layers, each shrinking the frames further."""
+    hidden_states, position_ids, new_len = patch_hooks.pyrd_resize(
+        hidden_states, position_ids, start, length, T, self.sa_pyrd_idx2size[layer.self_attn.layer_idx], type(self).sttm_resize_fn)
+    self.image_token_length = torch.tensor(new_len)                   # like the reference (:101): persists on the module
+    return hidden_states, position_ids, None, _KEEP_IDX
+
+
+def _hook_quadtree_vl(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    hidden_states, position_ids, _cache_pos, idx = patch_hooks.quadtree_merge_qwen2vl(
+        hidden_states, position_ids, start, length, T, _item(self.image_H), _item(self.image_W), type(self).sttm_merge_fn,
+        *_tree_args(self), slow_ver=self.sttm_slow_ver, merge_into_fn=_fused_merge_fn(type(self)))
+    return hidden_states, position_ids, None, idx
+
+
+def _hook_dycoke_vl(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    return _with_new_embeddings(patch_hooks.dycoke_merge(
+        hidden_states, position_ids, start, length, T, type(self).sttm_dycoke_fn, self.sa_prune_ratio, gather_positions=True))
+
+
+def _hook_tome_vl(self, layer, hidden_states, position_ids, position_embeddings, start, length, T):
+    return _with_new_embeddings(patch_hooks.tome_merge(
+        hidden_states, position_ids, start, length, T, _tome_merge_fn(type(self)), self.sa_prune_ratio, self.sa_tome_ver,
+        H=_item(self.image_H), W=_item(self.image_W), gather_positions=True))
+
+
+def _at_start_layer(self, i, merged):
+    return not merged and i == self.sa_start_layer_idx
+
+
+def _at_pyrd_layers(self, i, merged):
+    return i in self.sa_pyrd_llm_idxs
+
+
+def _batched_hook_qwen2(self, layer, hidden_states, position_ids, pads, attrs):
+    starts, lengths, Ts = attrs
+    return patch_hooks.quadtree_merge_llava_batched(
+        hidden_states, position_ids, pads, starts, lengths, Ts, type(self).sttm_merge_batch_fn, type(self).sttm_pack_fn,
+        *_tree_args(self), slow_ver=self.sttm_slow_ver, head_dim=_head_dim(self, layer))
+
+
+def _batched_hook_qwen2vl(self, layer, hidden_states, position_ids, pads, attrs):
+    starts, lengths, Ts, Hs, Ws = attrs
+    return patch_hooks.quadtree_merge_qwen2vl_batched(
+        hidden_states, position_ids, pads, starts, lengths, Ts, Hs, Ws, type(self).sttm_merge_batch_fn, type(self).sttm_pack_fn,
+        *_tree_args(self), slow_ver=self.sttm_slow_ver)
+
+
+def _positions_qwen2(position_ids, batched, attention_mask, inputs_embeds, past_key_values):
+    """(position ids [B or 1, L], no separate text ids)."""
+    if position_ids is None and batched:
+        position_ids = _positions_from_mask(attention_mask, inputs_embeds)
+    if position_ids is None:
+        seen = past_key_values.get_seq_length() if past_key_values is not None else 0
+        position_ids = (torch.arange(inputs_embeds.shape[1], device=inputs_embeds.device) + seen).unsqueeze(0)
+    return position_ids, None
+
+
+def _positions_qwen2vl(position_ids, batched, attention_mask, inputs_embeds, past_key_values):
+    """(3-D mRoPE ids [3, B, L], text ids [B, L] or None): default and 2-D ids are repeated on the three axes, a 4-row tensor is the
+    text row followed by the three mRoPE rows."""
+    if position_ids is None and batched:
+        position_ids = _positions_from_mask(attention_mask, inputs_embeds)[None].expand(3, -1, -1)
+    if position_ids is None:
+        seen = past_key_values.get_seq_length() if past_key_values is not None else 0
+        position_ids = torch.arange(inputs_embeds.shape[1], device=inputs_embeds.device) + seen
+        position_ids = position_ids.view(1, 1, -1).expand(3, inputs_embeds.shape[0], -1)
+    elif position_ids.ndim == 2:
+        position_ids = position_ids[None, ...].expand(3, position_ids.shape[0], -1)
+    if position_ids.ndim == 3 and position_ids.shape[0] == 4:
+        return position_ids[1:], position_ids[0]
+    return position_ids, None
+
+
+# What differs between the two model families.  `text_ids`: mask creation and the layers receive the text ids (None unless the
+# caller passed four rows), not the ids the rotary embedding is computed from.  `hooks`: pattern -> (fires(self, i, merged), hook);
+# a pattern that is not in the table takes the "tome" entry, like the reference's else branch.
+_Family = namedtuple("_Family", "row_attrs positions text_ids batched_hook hooks layers cache_out dycoke")
+
+_QWEN2 = _Family(
+    row_attrs=_QWEN2_ROW_ATTRS, positions=_positions_qwen2, text_ids=False, batched_hook=_batched_hook_qwen2,
+    hooks={"quadtree": (_at_start_layer, _hook_quadtree), "quadtree-abl-pos": (_at_start_layer, _hook_quadtree_abl_pos),
+           "dycoke-stage1": (_at_start_layer, _hook_dycoke), "dycoke": (_at_start_layer, _hook_dycoke),
+           "octree": (_at_start_layer, _hook_octree), "pyrd": (_at_pyrd_layers, _hook_pyrd), "tome": (_at_start_layer, _hook_tome)},
+    layers=lambda self: self.layers[: self.config.num_hidden_layers],
+    cache_out=lambda past_key_values, use_cache: past_key_values if use_cache else None,
+    dycoke=True)
+
+_QWEN2VL = _Family(
+    row_attrs=_QWEN2VL_ROW_ATTRS, positions=_positions_qwen2vl, text_ids=True, batched_hook=_batched_hook_qwen2vl,
+    hooks={"quadtree": (_at_start_layer, _hook_quadtree_vl), "dycoke-stage1": (_at_start_layer, _hook_dycoke_vl),
+           "tome": (_at_start_layer, _hook_tome_vl)},
+    layers=lambda self: self.layers,
+    cache_out=lambda past_key_values, use_cache: past_key_values,
+    dycoke=False)
+
+
+def _forward(self, fam, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs):
+    """transformers 5.x decoder forward of either family + the STTM / ToMe hook (prefill).  "quadtree" on B > 1 left-padded prompts
+    (or 1-D hook attributes) takes the batched hook; every other case runs the batch-1 hook of the pattern."""
     from transformers.cache_utils import DynamicCache
     from transformers.masking_utils import create_causal_mask, create_sliding_window_causal_mask
     from transformers.modeling_outputs import BaseModelOutputWithPast
@@ -252,23 +400,24 @@ def _qwen2_forward(self, input_ids=None, attention_mask=None, position_ids=None,
     if use_cache and past_key_values is None:
         past_key_values = DynamicCache(config=self.config)
     prefilling = _is_prefill(past_key_values)
-    rows = _batched_rows(self, inputs_embeds, attention_mask, prefilling, _QWEN2_ROW_ATTRS)
+    rows = _batched_rows(self, inputs_embeds, attention_mask, prefilling, fam.row_attrs)
+    fires = hook = dycoke_cache = None
     if prefilling:
         _reset_merged_mask(past_key_values)
-        if past_key_values is not None and getattr(past_key_values, "sttm_dycoke", None) is not None:
+        if fam.dycoke and past_key_values is not None and getattr(past_key_values, "sttm_dycoke", None) is not None:
             past_key_values.sttm_dycoke = None
-    elif self.sttm_pattern == "dycoke" and (step := _dycoke_step(self, inputs_embeds, past_key_values)) is not None:
+        if rows is None and getattr(self, "image_token_length", None) is not None:
+            fires, hook = fam.hooks.get(self.sttm_pattern) or fam.hooks["tome"]
+            if fam.dycoke and self.sttm_pattern == "dycoke":
+                dycoke_cache = past_key_values                        # stage 2 reads what stage 1 leaves there
+    elif fam.dycoke and self.sttm_pattern == "dycoke" and (step := _dycoke_step(self, inputs_embeds, past_key_values)) is not None:
         # restored by _qwen2_forward_with_merge
         self.config._sttm_dycoke_step = step
         self.config._attn_implementation = DYCOKE_ATTN
-    if position_ids is None and rows is not None:
-        position_ids = _positions_from_mask(attention_mask, inputs_embeds)
-    if position_ids is None:
-        seen = past_key_values.get_seq_length() if past_key_values is not None else 0
-        position_ids = (torch.arange(inputs_embeds.shape[1], device=inputs_embeds.device) + seen).unsqueeze(0)
+    position_ids, text_position_ids = fam.positions(position_ids, rows is not None, attention_mask, inputs_embeds, past_key_values)
     if not isinstance(mask_map := attention_mask, dict):
         mk = dict(config=self.config, inputs_embeds=inputs_embeds, attention_mask=attention_mask,
-                  past_key_values=past_key_values, position_ids=position_ids)
+                  past_key_values=past_key_values, position_ids=text_position_ids if fam.text_ids else position_ids)
         mask_map = {"full_attention": create_causal_mask(**mk)}
         if getattr(self, "has_sliding_layers", False):
             mask_map["sliding_attention"] = create_sliding_window_causal_mask(**mk)
@@ -277,159 +426,71 @@ def _qwen2_forward(self, input_ids=None, attention_mask=None, position_ids=None,
     hidden_states = inputs_embeds
     position_embeddings = self.rotary_emb(hidden_states, position_ids)
     merged = False
-    for i, layer in enumerate(self.layers[: self.config.num_hidden_layers]):
+    for i, layer in enumerate(fam.layers(self)):
         if late_masks is not None and i == self.sa_start_layer_idx:
             mask_map = late_masks
         if rows is not None and not merged and i == self.sa_start_layer_idx:
-            pads, (starts, lengths, Ts) = rows
-            head_dim = layer.self_attn.head_dim if self.sim_per_head else None
             L = hidden_states.size(1)
-            hidden_states, mask2d, position_ids, idx = patch_hooks.quadtree_merge_llava_batched(
-                hidden_states, position_ids, pads, starts, lengths, Ts, type(self).sttm_merge_batch_fn, type(self).sttm_pack_fn,
-                self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
-                slow_ver=self.sttm_slow_ver, head_dim=head_dim)
+            hidden_states, mask2d, position_ids, idx = fam.batched_hook(self, layer, hidden_states, position_ids, *rows)
+            if text_position_ids is not None:
+                text_position_ids = _truncate_rows(text_position_ids, rows[0], mask2d, L)
             self.merged_token_1d_idx = idx
             position_embeddings = self.rotary_emb(hidden_states, position_ids)
             mask_map = _merged_layout_masks(self, mask_map, hidden_states, mask2d, None)
             _keep_merged_mask(past_key_values, mask2d, L)
             merged = True
-        elif (prefilling and self.sttm_pattern == "pyrd" and i in self.sa_pyrd_llm_idxs
-                and getattr(self, "image_token_length", None) is not None):
-            # fixed-size pyramid baseline: may fire at several layers, each shrinking the frames further
+        elif hook is not None and fires(self, i, merged):
             start, length, T = _item(self.image_token_start_index), _item(self.image_token_length), _item(self.num_frame)
-            hidden_states, position_ids, new_len = patch_hooks.pyrd_resize(
-                hidden_states, position_ids, start, length, T, self.sa_pyrd_idx2size[i], type(self).sttm_resize_fn)
-            self.image_token_length = torch.tensor(new_len)              # like the reference (:101): persists on the module
-            position_embeddings = self.rotary_emb(hidden_states, position_ids)
-            mask_map = _rebuild_masks(self, mask_map, hidden_states, past_key_values, position_ids)
-        elif (prefilling and not merged and self.sttm_pattern != "pyrd" and i == self.sa_start_layer_idx
-                and getattr(self, "image_token_length", None) is not None):
-            start, length, T = _item(self.image_token_start_index), _item(self.image_token_length), _item(self.num_frame)
-            if self.sttm_pattern == "quadtree-abl-pos":
-                head_dim = layer.self_attn.head_dim if self.sim_per_head else None
-                hidden_states, position_ids, position_embeddings, idx = patch_hooks.quadtree_merge_abl_pos(
-                    hidden_states, position_ids, position_embeddings, start, length, T, type(self).sttm_merge_fn,
-                    self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
-                    self.pos_emb_ver, self.pos_emb_weighted_avg, self.rotary_emb, slow_ver=self.sttm_slow_ver, head_dim=head_dim)
-            elif self.sttm_pattern == "quadtree":
-                head_dim = layer.self_attn.head_dim if self.sim_per_head else None
-                hidden_states, position_ids, idx = patch_hooks.quadtree_merge_llava(
-                    hidden_states, position_ids, start, length, T, type(self).sttm_merge_fn,
-                    self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
-                    slow_ver=self.sttm_slow_ver, head_dim=head_dim,
-                    merge_into_fn=_fused_merge_fn(type(self)))
-            elif self.sttm_pattern in ("dycoke-stage1", "dycoke"):
-                hidden_states, position_ids, idx = patch_hooks.dycoke_merge(
-                    hidden_states, position_ids, start, length, T, type(self).sttm_dycoke_fn, self.sa_prune_ratio)
-                if self.sttm_pattern == "dycoke" and past_key_values is not None:
-                    past_key_values.sttm_dycoke = (start, length)     # :370-371: the visual token count BEFORE stage 1
-            elif self.sttm_pattern == "octree":
-                hidden_states, position_ids = patch_hooks.octree_merge(
-                    hidden_states, position_ids, start, length, T, type(self).sttm_octree_fn, self.sa_tree_thresh,
-                    self.sa_tree_root_level)
-                idx = None                                            # the reference's octree hook keeps no token index
-            else:
-                hidden_states, position_ids, idx = patch_hooks.tome_merge(
-                    hidden_states, position_ids, start, length, T, _tome_merge_fn(type(self)), self.sa_prune_ratio, self.sa_tome_ver)
-            self.merged_token_1d_idx = idx
-            if self.sttm_pattern != "quadtree-abl-pos":               # that hook decides its own position embeddings
+            hidden_states, position_ids, position_embeddings, idx = hook(
+                self, layer, hidden_states, position_ids, position_embeddings, start, length, T)
+            if text_position_ids is not None:
+                text_position_ids = text_position_ids[..., :hidden_states.size(1)]
+            if idx is not _KEEP_IDX:
+                self.merged_token_1d_idx = idx
+                merged = True
+            if dycoke_cache is not None:
+                dycoke_cache.sttm_dycoke = (start, length)            # :370-371: the visual token count BEFORE stage 1
+            if position_embeddings is None:
                 position_embeddings = self.rotary_emb(hidden_states, position_ids)
             # batch-1 prefill without padding: the shorter sequence is plain causal
-            mask_map = _rebuild_masks(self, mask_map, hidden_states, past_key_values, position_ids)
-            merged = True
+            mask_map = _rebuild_masks(self, mask_map, hidden_states)
         hidden_states = layer(hidden_states, attention_mask=mask_map[self.config.layer_types[i]],
-                              position_embeddings=position_embeddings, position_ids=position_ids,
+                              position_embeddings=position_embeddings,
+                              position_ids=text_position_ids if fam.text_ids else position_ids,
                               past_key_values=past_key_values, use_cache=use_cache, **kwargs)
     hidden_states = self.norm(hidden_states)
-    return BaseModelOutputWithPast(last_hidden_state=hidden_states, past_key_values=past_key_values if use_cache else None)
+    return BaseModelOutputWithPast(last_hidden_state=hidden_states, past_key_values=fam.cache_out(past_key_values, use_cache))
+
+
+def _qwen2_forward_with_merge(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
+                              inputs_embeds=None, use_cache=None, **kwargs):
+    """Qwen2Model.forward + the hook.  A "dycoke" decode step runs with the dispatching attention function and its per-forward
+    state on the config; both are put back whatever happens."""
+    if self.sttm_pattern != "dycoke":
+        return _forward(self, _QWEN2, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs)
+    x = inputs_embeds if inputs_embeds is not None else input_ids
+    if x is not None and x.shape[0] != 1:
+        raise NotImplementedError(f"DyCoke reads row 0 of the attention matrix (`[0, -1]`) and prunes one video: batch size 1 only, got {x.shape[0]}")
+    cfg = self.config
+    saved = cfg._attn_implementation
+    try:
+        return _forward(self, _QWEN2, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs)
+    finally:
+        if cfg._attn_implementation != saved:
+            cfg._attn_implementation = saved
+        if getattr(cfg, "_sttm_dycoke_step", None) is not None:
+            cfg._sttm_dycoke_step = None
 
 
 def _qwen2vl_forward_with_merge(self, input_ids=None, attention_mask=None, position_ids=None, past_key_values=None,
                                 inputs_embeds=None, use_cache=None, **kwargs):
-    """transformers 5.x Qwen2VLTextModel.forward + the STTM / ToMe hook: 3-D mRoPE position ids are GATHERED by the
-    merged-token index (token_merging_qwen2vl_monkey_patch/quadtree_attn_monkey_patch.py:109-113); H and W come from
+    """Qwen2VLTextModel.forward + the hook: 3-D mRoPE position ids are GATHERED by the merged-token index
+    (token_merging_qwen2vl_monkey_patch/quadtree_attn_monkey_patch.py:109-113); H and W come from
     `self.image_H / self.image_W` (llava/model/qwen2vl/modeling_qwen2vl.py:1919-1920)."""
-    from transformers.cache_utils import DynamicCache
-    from transformers.masking_utils import create_causal_mask, create_sliding_window_causal_mask
-    from transformers.modeling_outputs import BaseModelOutputWithPast
-    if (input_ids is None) ^ (inputs_embeds is not None):
-        raise ValueError("You must specify exactly one of input_ids or inputs_embeds")
-    if use_cache and past_key_values is None:
-        past_key_values = DynamicCache(config=self.config)
-    if inputs_embeds is None:
-        inputs_embeds = self.embed_tokens(input_ids)
-    prefilling = _is_prefill(past_key_values)
-    rows = _batched_rows(self, inputs_embeds, attention_mask, prefilling, _QWEN2VL_ROW_ATTRS)
-    if prefilling:
-        _reset_merged_mask(past_key_values)
-    if position_ids is None and rows is not None:
-        position_ids = _positions_from_mask(attention_mask, inputs_embeds)[None].expand(3, -1, -1)
-    if position_ids is None:
-        seen = past_key_values.get_seq_length() if past_key_values is not None else 0
-        position_ids = torch.arange(inputs_embeds.shape[1], device=inputs_embeds.device) + seen
-        position_ids = position_ids.view(1, 1, -1).expand(3, inputs_embeds.shape[0], -1)
-    elif position_ids.ndim == 2:
-        position_ids = position_ids[None, ...].expand(3, position_ids.shape[0], -1)
-    text_position_ids = None
-    if position_ids.ndim == 3 and position_ids.shape[0] == 4:
-        text_position_ids = position_ids[0]
-        position_ids = position_ids[1:]
-    if not isinstance(mask_map := attention_mask, dict):
-        mk = dict(config=self.config, inputs_embeds=inputs_embeds, attention_mask=attention_mask,
-                  past_key_values=past_key_values, position_ids=text_position_ids)
-        mask_map = {"full_attention": create_causal_mask(**mk)}
-        if getattr(self, "has_sliding_layers", False):
-            mask_map["sliding_attention"] = create_sliding_window_causal_mask(**mk)
-    late_masks = None if prefilling else _decode_masks(self, mask_map, inputs_embeds, attention_mask, past_key_values)
-    hidden_states = inputs_embeds
-    position_embeddings = self.rotary_emb(hidden_states, position_ids)
-    merged = False
-    for i, layer in enumerate(self.layers):
-        if late_masks is not None and i == self.sa_start_layer_idx:
-            mask_map = late_masks
-        if rows is not None and not merged and i == self.sa_start_layer_idx:
-            pads, (starts, lengths, Ts, Hs, Ws) = rows
-            L = hidden_states.size(1)
-            hidden_states, mask2d, position_ids, idx = patch_hooks.quadtree_merge_qwen2vl_batched(
-                hidden_states, position_ids, pads, starts, lengths, Ts, Hs, Ws, type(self).sttm_merge_batch_fn, type(self).sttm_pack_fn,
-                self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
-                slow_ver=self.sttm_slow_ver)
-            if text_position_ids is not None:
-                text_position_ids = _truncate_rows(text_position_ids, pads, mask2d, L)
-            self.merged_token_1d_idx = idx
-            position_embeddings = self.rotary_emb(hidden_states, position_ids)
-            mask_map = _merged_layout_masks(self, mask_map, hidden_states, mask2d, None)
-            _keep_merged_mask(past_key_values, mask2d, L)
-            merged = True
-        elif prefilling and not merged and i == self.sa_start_layer_idx and getattr(self, "image_token_length", None) is not None:
-            start, length, T = _item(self.image_token_start_index), _item(self.image_token_length), _item(self.num_frame)
-            H, W = _item(self.image_H), _item(self.image_W)
-            if self.sttm_pattern == "quadtree":
-                hidden_states, position_ids, _cache_pos, idx = patch_hooks.quadtree_merge_qwen2vl(
-                    hidden_states, position_ids, start, length, T, H, W, type(self).sttm_merge_fn,
-                    self.sa_tree_thresh, self.sa_tree_temporal_thresh, self.sa_tree_root_level, self.sa_tree_weighted_avg,
-                    slow_ver=self.sttm_slow_ver, merge_into_fn=_fused_merge_fn(type(self)))
-            elif self.sttm_pattern == "dycoke-stage1":
-                hidden_states, position_ids, idx = patch_hooks.dycoke_merge(
-                    hidden_states, position_ids, start, length, T, type(self).sttm_dycoke_fn, self.sa_prune_ratio,
-                    gather_positions=True)
-            else:
-                hidden_states, position_ids, idx = patch_hooks.tome_merge(
-                    hidden_states, position_ids, start, length, T, _tome_merge_fn(type(self)), self.sa_prune_ratio,
-                    self.sa_tome_ver, H=H, W=W, gather_positions=True)
-            if text_position_ids is not None:
-                text_position_ids = text_position_ids[..., :hidden_states.size(1)]
-            self.merged_token_1d_idx = idx
-            position_embeddings = self.rotary_emb(hidden_states, position_ids)
-            mask_map = _rebuild_masks(self, mask_map, hidden_states, past_key_values, text_position_ids)
-            merged = True
-        hidden_states = layer(hidden_states, attention_mask=mask_map[self.config.layer_types[i]],
-                              position_embeddings=position_embeddings, position_ids=text_position_ids,
-                              past_key_values=past_key_values, use_cache=use_cache, **kwargs)
-    hidden_states = self.norm(hidden_states)
-    return BaseModelOutputWithPast(last_hidden_state=hidden_states, past_key_values=past_key_values)
+    return _forward(self, _QWEN2VL, input_ids, attention_mask, position_ids, past_key_values, inputs_embeds, use_cache, **kwargs)
 
 
+# ---- installers --------------------------------------------------------------------------------------------------------------
 def _qwen2_model_class():
     import transformers.models.qwen2.modeling_qwen2 as m
     return m.Qwen2Model
@@ -443,86 +504,86 @@ def _qwen2vl_model_class():
         return None
 
 
-def _fused_merge_fn(cls):
-    """Fused slice -> merge -> concat (the kernels write the merged rows into the new hidden-state buffer) is used
-    whenever the merge function is the library's own; an injected `sttm_merge_fn` (tests) takes the plain path."""
-    return get_quadtree_features_into if cls.sttm_merge_fn is get_quadtree_features else None
+def _install(cls, forward, pattern, attrs, injection_defaults):
+    """The class-attribute mechanism of every pattern: configuration as class attributes, injection points (`sttm_*_fn`: tests put
+    the CPU oracle there) filled only where absent (`_resolve`), the original forward saved once, `forward` replaced."""
+    cls.sttm_pattern = pattern
+    for name, value in attrs.items():
+        setattr(cls, name, value)
+    for name, default in injection_defaults.items():
+        if not hasattr(cls, name):
+            setattr(cls, name, staticmethod(_resolve(default)))
+    if not hasattr(cls, "_sttm_original_forward"):
+        cls._sttm_original_forward = cls.forward
+    cls.forward = forward
 
 
-def _install_batched_fns(cls):
-    """Injection points of the batched hook, next to `sttm_merge_fn`: the merge of the B videos and the ragged pack (tests put the
-    CPU oracle and a torch restatement here)."""
-    if not hasattr(cls, "sttm_merge_batch_fn"):
-        cls.sttm_merge_batch_fn = staticmethod(get_quadtree_features_batch_reused)
-    if not hasattr(cls, "sttm_pack_fn"):
-        cls.sttm_pack_fn = staticmethod(pack_merged_batch)
+# the batched hook's injection points sit next to `sttm_merge_fn`: the merge of the B videos and the ragged pack
+_QUADTREE_FNS = {"sttm_merge_fn": get_quadtree_features, "sttm_merge_batch_fn": get_quadtree_features_batch_reused,
+                 "sttm_pack_fn": pack_merged_batch}
+_DYCOKE_FNS = {"sttm_dycoke_fn": (".dycoke_merger", "dycoke_ttm")}
+
+
+def _install_quadtree(cls, forward, pattern, sa_start_layer_idx, sa_tree_thresh, sa_tree_temporal_thresh, sa_tree_root_level,
+                      sa_tree_weighted_avg, sttm_slow_ver, **more):
+    _install(cls, forward, pattern, dict(
+        sa_start_layer_idx=sa_start_layer_idx, sa_tree_thresh=sa_tree_thresh, sa_tree_temporal_thresh=sa_tree_temporal_thresh,
+        sa_tree_root_level=sa_tree_root_level, sa_tree_weighted_avg=sa_tree_weighted_avg, sttm_slow_ver=sttm_slow_ver, **more),
+        _QUADTREE_FNS)
 
 
 def replace_qwen2_with_quadtree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90, sa_tree_temporal_thresh=-1.0,
                                      sa_tree_root_level=0, sa_tree_weighted_avg=False, sttm_slow_ver=False,
                                      sim_per_head=False, **kwargs):
     print("Replace Qwen2 attention path by QuadTree (STTM) token merging [sttm_amd / MI355X]")
-    cls = _qwen2_model_class()
-    cls.sttm_pattern = "quadtree"
-    cls.sa_start_layer_idx = sa_start_layer_idx
-    cls.sa_tree_thresh = sa_tree_thresh
-    cls.sa_tree_temporal_thresh = sa_tree_temporal_thresh
-    cls.sa_tree_root_level = sa_tree_root_level
-    cls.sa_tree_weighted_avg = sa_tree_weighted_avg
-    cls.sttm_slow_ver = sttm_slow_ver
-    cls.sim_per_head = sim_per_head
-    if not hasattr(cls, "sttm_merge_fn"):
-        cls.sttm_merge_fn = staticmethod(get_quadtree_features)
-    _install_batched_fns(cls)
-    if not hasattr(cls, "_sttm_original_forward"):
-        cls._sttm_original_forward = cls.forward
-    cls.forward = _qwen2_forward_with_merge
+    _install_quadtree(_qwen2_model_class(), _qwen2_forward_with_merge, "quadtree", sa_start_layer_idx, sa_tree_thresh,
+                      sa_tree_temporal_thresh, sa_tree_root_level, sa_tree_weighted_avg, sttm_slow_ver, sim_per_head=sim_per_head)
 
 
 def replace_qwen2_with_quadtree_attn_for_abl_pos(sa_start_layer_idx=0, sa_tree_thresh=0.90, sa_tree_temporal_thresh=-1.0,
                                                  sa_tree_root_level=0, sa_tree_weighted_avg=False, sttm_slow_ver=False,
                                                  sim_per_head=False, pos_emb_ver=0, pos_emb_weighted_avg=False, **kwargs):
     """quadtree_attn_monkey_patch_for_abl_pos.py:193-205."""
-    replace_qwen2_with_quadtree_attn(sa_start_layer_idx, sa_tree_thresh, sa_tree_temporal_thresh, sa_tree_root_level,
-                                     sa_tree_weighted_avg, sttm_slow_ver, sim_per_head)
-    cls = _qwen2_model_class()
-    cls.sttm_pattern = "quadtree-abl-pos"
-    cls.pos_emb_ver = pos_emb_ver
-    cls.pos_emb_weighted_avg = pos_emb_weighted_avg
+    print("Replace Qwen2 attention path by QuadTree (STTM) token merging [sttm_amd / MI355X]")
+    _install_quadtree(_qwen2_model_class(), _qwen2_forward_with_merge, "quadtree-abl-pos", sa_start_layer_idx, sa_tree_thresh,
+                      sa_tree_temporal_thresh, sa_tree_root_level, sa_tree_weighted_avg, sttm_slow_ver, sim_per_head=sim_per_head,
+                      pos_emb_ver=pos_emb_ver, pos_emb_weighted_avg=pos_emb_weighted_avg)
+
+
+def replace_qwen2vl_with_quadtree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90, sa_tree_temporal_thresh=-1.0,
+                                       sa_tree_root_level=0, sa_tree_weighted_avg=False, sttm_slow_ver=False, **kwargs):
+    """Qwen2-VL text model (transformers 5.x `Qwen2VLTextModel`): same class-attribute mechanism, forward replaced by
+    `_qwen2vl_forward_with_merge` (3-D position-id gather).  No `sim_per_head` here."""
+    cls = _qwen2vl_model_class()
+    if cls is None:
+        return
+    print("Replace Qwen2-VL attention path by QuadTree (STTM) token merging [sttm_amd / MI355X]")
+    _install_quadtree(cls, _qwen2vl_forward_with_merge, "quadtree", sa_start_layer_idx, sa_tree_thresh, sa_tree_temporal_thresh,
+                      sa_tree_root_level, sa_tree_weighted_avg, sttm_slow_ver)
 
 
 def replace_qwen2_with_octree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90, sa_tree_root_level=0, **kwargs):
     """octree_attn_monkey_patch.py:163-168."""
     print("Replace Qwen2 attention path by OcTree token merging [sttm_amd / MI355X]")
-    cls = _qwen2_model_class()
-    cls.sttm_pattern = "octree"
-    cls.sa_start_layer_idx = sa_start_layer_idx
-    cls.sa_tree_thresh = sa_tree_thresh
-    cls.sa_tree_root_level = sa_tree_root_level
-    if not hasattr(cls, "sttm_octree_fn"):
-        from .octree_utils import get_octree_features
-        cls.sttm_octree_fn = staticmethod(get_octree_features)
-    if not hasattr(cls, "_sttm_original_forward"):
-        cls._sttm_original_forward = cls.forward
-    cls.forward = _qwen2_forward_with_merge
-
-
-def _install_dycoke(cls, forward, sa_start_layer_idx, sa_prune_ratio):
-    cls.sttm_pattern = "dycoke-stage1"
-    cls.sa_start_layer_idx = sa_start_layer_idx
-    cls.sa_prune_ratio = sa_prune_ratio
-    if not hasattr(cls, "sttm_dycoke_fn"):
-        from .dycoke_merger import dycoke_ttm
-        cls.sttm_dycoke_fn = staticmethod(dycoke_ttm)
-    if not hasattr(cls, "_sttm_original_forward"):
-        cls._sttm_original_forward = cls.forward
-    cls.forward = forward
+    _install(_qwen2_model_class(), _qwen2_forward_with_merge, "octree",
+             dict(sa_start_layer_idx=sa_start_layer_idx, sa_tree_thresh=sa_tree_thresh, sa_tree_root_level=sa_tree_root_level),
+             {"sttm_octree_fn": (".octree_utils", "get_octree_features")})
 
 
 def replace_qwen2_with_dycoke_stage1_attn(sa_start_layer_idx=0, sa_prune_ratio=0.7, **kwargs):
     """dycoke_stage1_attn_monkey_patch.py:165-169."""
     print("Replace Qwen2 attention path by DyCoke stage-1 pruning [sttm_amd / MI355X]")
-    _install_dycoke(_qwen2_model_class(), _qwen2_forward_with_merge, sa_start_layer_idx, sa_prune_ratio)
+    _install(_qwen2_model_class(), _qwen2_forward_with_merge, "dycoke-stage1",
+             dict(sa_start_layer_idx=sa_start_layer_idx, sa_prune_ratio=sa_prune_ratio), _DYCOKE_FNS)
+
+
+def replace_qwen2vl_with_dycoke_stage1_attn(sa_start_layer_idx=0, sa_prune_ratio=0.7, **kwargs):
+    """token_merging_qwen2vl_monkey_patch/dycoke_stage1_attn_monkey_patch.py:165-168."""
+    cls = _qwen2vl_model_class()
+    if cls is None:
+        return
+    _install(cls, _qwen2vl_forward_with_merge, "dycoke-stage1",
+             dict(sa_start_layer_idx=sa_start_layer_idx, sa_prune_ratio=sa_prune_ratio), _DYCOKE_FNS)
 
 
 def replace_qwen2_with_dycoke_attn(sa_start_layer_idx=0, sa_prune_ratio=0.7, dycoke_l=3, dycoke_p=0.8, **kwargs):
@@ -533,102 +594,37 @@ def replace_qwen2_with_dycoke_attn(sa_start_layer_idx=0, sa_prune_ratio=0.7, dyc
         raise ValueError(f"dycoke_p = {dycoke_p} must lie in [0, 1]: int(n0 * (1 - dycoke_p)) visual keys are kept")
     print("Replace Qwen2 attention path by DyCoke (stage 1 + decode-time KV selection) [sttm_amd / MI355X]")
     from transformers.modeling_utils import AttentionInterface
-    cls = _qwen2_model_class()
-    _install_dycoke(cls, _qwen2_forward_with_merge, sa_start_layer_idx, sa_prune_ratio)
-    cls.sttm_pattern = "dycoke"
-    cls.dycoke_l = int(dycoke_l)
-    cls.dycoke_p = float(dycoke_p)
-    for name, fn in zip(_DECODE_FNS, _default_decode_fns()):
-        if not hasattr(cls, name):
-            setattr(cls, name, staticmethod(fn))
+    _install(_qwen2_model_class(), _qwen2_forward_with_merge, "dycoke",
+             dict(sa_start_layer_idx=sa_start_layer_idx, sa_prune_ratio=sa_prune_ratio, dycoke_l=int(dycoke_l), dycoke_p=float(dycoke_p)),
+             {**_DYCOKE_FNS, **_DECODE_DEFAULTS})
     AttentionInterface.register(DYCOKE_ATTN, _dycoke_attention)
-
-
-_DECODE_FNS = ("sttm_decode_scores_fn", "sttm_decode_select_fn", "sttm_decode_attn_fn")
-
-
-def replace_qwen2vl_with_dycoke_stage1_attn(sa_start_layer_idx=0, sa_prune_ratio=0.7, **kwargs):
-    """token_merging_qwen2vl_monkey_patch/dycoke_stage1_attn_monkey_patch.py:165-168."""
-    cls = _qwen2vl_model_class()
-    if cls is None:
-        return
-    _install_dycoke(cls, _qwen2vl_forward_with_merge, sa_start_layer_idx, sa_prune_ratio)
 
 
 def replace_qwen2_with_pyrd_attn(sa_pyrd_loc_list=[2], sa_pyrd_size_list=[10], **kwargs):
     """pyrd_attn_monkey_patch.py:167-173: resize every frame to size x size (nearest) before the listed decoder layers."""
     print("Replace Qwen2 attention path by Pyramid token merging [sttm_amd / MI355X]")
     assert len(sa_pyrd_loc_list) == len(sa_pyrd_size_list)
-    cls = _qwen2_model_class()
-    cls.sttm_pattern = "pyrd"
-    cls.sa_pyrd_llm_idxs = list(sa_pyrd_loc_list)
-    cls.sa_pyrd_idx2size = {sa_pyrd_loc_list[i]: sa_pyrd_size_list[i] for i in range(len(sa_pyrd_loc_list))}
-    if not hasattr(cls, "sttm_resize_fn"):
-        from .upstream import resize_nearest
-        cls.sttm_resize_fn = staticmethod(resize_nearest)
-    if not hasattr(cls, "_sttm_original_forward"):
-        cls._sttm_original_forward = cls.forward
-    cls.forward = _qwen2_forward_with_merge
+    _install(_qwen2_model_class(), _qwen2_forward_with_merge, "pyrd",
+             dict(sa_pyrd_llm_idxs=list(sa_pyrd_loc_list), sa_pyrd_idx2size=dict(zip(sa_pyrd_loc_list, sa_pyrd_size_list))),
+             {"sttm_resize_fn": (".upstream", "resize_nearest")})
 
 
-def _tome_merge_fn(cls):
-    """The merge function the ToMe branch hands to patch_hooks.tome_merge: `sttm_tome_fn(video, prune_ratio, tome_ver)` as the
-    reference dispatches it, or -- when the installer was given sa_tome_snippet_size -- per-snippet ToMe, which ignores tome_ver."""
-    size = getattr(cls, "sa_tome_snippet_size", None)
-    if size is None:
-        return cls.sttm_tome_fn
-    fn = cls.sttm_tome_snippet_fn
-    return lambda video, prune_ratio, _tome_ver: fn(video, prune_ratio, size)
-
-
-def _install_tome_snippet(cls, sa_tome_snippet_size):
+def _install_tome(cls, forward, sa_start_layer_idx, sa_prune_ratio, sa_tome_ver, sa_tome_snippet_size):
     """sa_tome_snippet_size: None = the reference's tome_ver dispatch (where "frame" raises for T > 1); an integer S >= 1 = working
     per-frame (S = 1) / per-snippet ToMe (get_tome_features_snippet)."""
+    fns = {"sttm_tome_fn": get_tome_features}
     if sa_tome_snippet_size is not None:
         if isinstance(sa_tome_snippet_size, bool) or int(sa_tome_snippet_size) != sa_tome_snippet_size or sa_tome_snippet_size < 1:
             raise ValueError(f"sa_tome_snippet_size must be an integer >= 1 or None, got {sa_tome_snippet_size!r}")
         sa_tome_snippet_size = int(sa_tome_snippet_size)
-        if not hasattr(cls, "sttm_tome_snippet_fn"):
-            cls.sttm_tome_snippet_fn = staticmethod(get_tome_features_snippet)
-    cls.sa_tome_snippet_size = sa_tome_snippet_size
+        fns["sttm_tome_snippet_fn"] = get_tome_features_snippet
+    _install(cls, forward, "tome", dict(sa_start_layer_idx=sa_start_layer_idx, sa_prune_ratio=sa_prune_ratio, sa_tome_ver=sa_tome_ver,
+                                        sa_tome_snippet_size=sa_tome_snippet_size), fns)
 
 
 def replace_qwen2_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa_tome_ver="frame", sa_tome_snippet_size=None, **kwargs):
     print("Replace Qwen2 attention path by ToMe token merging [sttm_amd / MI355X]")
-    cls = _qwen2_model_class()
-    cls.sttm_pattern = "tome"
-    cls.sa_start_layer_idx = sa_start_layer_idx
-    cls.sa_prune_ratio = sa_prune_ratio
-    cls.sa_tome_ver = sa_tome_ver
-    if not hasattr(cls, "sttm_tome_fn"):
-        cls.sttm_tome_fn = staticmethod(get_tome_features)
-    _install_tome_snippet(cls, sa_tome_snippet_size)
-    if not hasattr(cls, "_sttm_original_forward"):
-        cls._sttm_original_forward = cls.forward
-    cls.forward = _qwen2_forward_with_merge
-
-
-def replace_qwen2vl_with_quadtree_attn(sa_start_layer_idx=0, sa_tree_thresh=0.90, sa_tree_temporal_thresh=-1.0,
-                                       sa_tree_root_level=0, sa_tree_weighted_avg=False, sttm_slow_ver=False, **kwargs):
-    """Qwen2-VL text model (transformers 5.x `Qwen2VLTextModel`): same class-attribute mechanism, forward replaced by
-    `_qwen2vl_forward_with_merge` (3-D position-id gather)."""
-    cls = _qwen2vl_model_class()
-    if cls is None:
-        return
-    print("Replace Qwen2-VL attention path by QuadTree (STTM) token merging [sttm_amd / MI355X]")
-    cls.sttm_pattern = "quadtree"
-    cls.sa_start_layer_idx = sa_start_layer_idx
-    cls.sa_tree_thresh = sa_tree_thresh
-    cls.sa_tree_temporal_thresh = sa_tree_temporal_thresh
-    cls.sa_tree_root_level = sa_tree_root_level
-    cls.sa_tree_weighted_avg = sa_tree_weighted_avg
-    cls.sttm_slow_ver = sttm_slow_ver
-    if not hasattr(cls, "sttm_merge_fn"):
-        cls.sttm_merge_fn = staticmethod(get_quadtree_features)
-    _install_batched_fns(cls)
-    if not hasattr(cls, "_sttm_original_forward"):
-        cls._sttm_original_forward = cls.forward
-    cls.forward = _qwen2vl_forward_with_merge
+    _install_tome(_qwen2_model_class(), _qwen2_forward_with_merge, sa_start_layer_idx, sa_prune_ratio, sa_tome_ver, sa_tome_snippet_size)
 
 
 def replace_qwen2vl_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa_tome_ver="frame", sa_tome_snippet_size=None, **kwargs):
@@ -636,16 +632,7 @@ def replace_qwen2vl_with_tome_attn(sa_start_layer_idx=0, sa_prune_ratio=0.50, sa
     if cls is None:
         return
     print("Replace Qwen2-VL attention path by ToMe token merging [sttm_amd / MI355X]")
-    cls.sttm_pattern = "tome"
-    cls.sa_start_layer_idx = sa_start_layer_idx
-    cls.sa_prune_ratio = sa_prune_ratio
-    cls.sa_tome_ver = sa_tome_ver
-    if not hasattr(cls, "sttm_tome_fn"):
-        cls.sttm_tome_fn = staticmethod(get_tome_features)
-    _install_tome_snippet(cls, sa_tome_snippet_size)
-    if not hasattr(cls, "_sttm_original_forward"):
-        cls._sttm_original_forward = cls.forward
-    cls.forward = _qwen2vl_forward_with_merge
+    _install_tome(cls, _qwen2vl_forward_with_merge, sa_start_layer_idx, sa_prune_ratio, sa_tome_ver, sa_tome_snippet_size)
 
 
 def restore_qwen2():

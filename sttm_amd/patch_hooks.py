@@ -22,6 +22,21 @@ def split_prompt(hidden_states, start, length):
     return hidden_states[:, :start], hidden_states[:, start:end], hidden_states[:, end:]
 
 
+def _splice(hidden_states, start, length, feat):
+    """system ++ feat ++ instruction: the rows feat [N', C] in place of the visual slice."""
+    sys_f, _, inst_f = split_prompt(hidden_states, start, length)
+    return torch.cat([sys_f, feat.unsqueeze(0), inst_f], dim=1)
+
+
+def _positions_after(position_ids, start, length, n, idx=None):
+    """Position ids of the spliced sequence of n tokens.  idx None: [B, S] ids TRUNCATED to n.  Otherwise the visual columns are
+    GATHERED by idx along the last axis ([B, S] or 3-D mRoPE [3, B, S] ids), system / instruction ids kept."""
+    if idx is None:
+        return position_ids[:, :n]
+    end = start + length
+    return torch.cat([position_ids[..., :start], position_ids[..., start:end][..., idx.long()], position_ids[..., end:]], dim=-1)
+
+
 def _merge_concat(hidden_states, start, length, video, merge_fn, merge_into_fn, args, kwargs):
     """system ++ merge(video) ++ instruction  (quadtree_attn_monkey_patch.py:101-105).
 
@@ -69,8 +84,7 @@ def quadtree_merge_qwen2vl(hidden_states, position_ids, start, length, T, H, W, 
                                       (threshold, temporal_thresh, root_level, weighted_avg), dict(slow_ver=slow_ver))
     if idx is None:
         idx = tlbr[:, 0] * (H * W) + tlbr[:, 1] * W + tlbr[:, 2]
-    vis_pos = position_ids[:, :, start:end][:, :, idx.long()]
-    pos = torch.cat([position_ids[:, :, :start], vis_pos, position_ids[:, :, end:]], dim=-1)
+    pos = _positions_after(position_ids, start, length, merged.size(1), idx)
     cache_position = torch.arange(merged.size(1), device=merged.device, dtype=torch.int)      # :114
     return merged, pos, cache_position, idx
 
@@ -123,59 +137,42 @@ def tome_merge(hidden_states, position_ids, start, length, T, merge_fn, prune_ra
     [B, S] are TRUNCATED to the new length (:105).  Qwen2-VL (token_merging_qwen2vl_monkey_patch/tome_attn_monkey_patch.py:
     88-111, gather_positions=True): H, W come from the module, and the 3-D mRoPE ids [3, B, S] of the visual part are
     GATHERED by the ToMe token index, system / instruction ids kept (:105-108)."""
-    sys_f, vis_f, inst_f = split_prompt(hidden_states, start, length)
-    end = start + length
     if H is None:
         H = int(math.sqrt(length // T))
         W = (length // T) // H
-    video = _video_view(vis_f[0], T, H, W)
+    video = _video_view(hidden_states[0, start:start + length], T, H, W)
     feat, token_idx = merge_fn(video, prune_ratio, tome_ver)
-    merged = torch.cat([sys_f, feat.unsqueeze(0), inst_f], dim=1)
-    if gather_positions:
-        vis_pos = position_ids[:, :, start:end][:, :, token_idx]
-        pos = torch.cat([position_ids[:, :, :start], vis_pos, position_ids[:, :, end:]], dim=-1)
-    else:
-        pos = position_ids[:, :merged.size(1)]
-    return merged, pos, token_idx
+    merged = _splice(hidden_states, start, length, feat)
+    return merged, _positions_after(position_ids, start, length, merged.size(1), token_idx if gather_positions else None), token_idx
 
 
 def pyrd_resize(hidden_states, position_ids, start, length, T, tgt_size, resize_fn):
     """The "pyrd" baseline (pyrd_attn_monkey_patch.py:88-112): every frame of the visual slice is resized to
     tgt_size x tgt_size with F.interpolate's default (nearest) mode.  resize_fn(tokens [T, H*W, C], H, W, (s, s)).
     Returns (hidden_states, position_ids[:, :S'], new visual length)."""
-    sys_f, vis_f, inst_f = split_prompt(hidden_states, start, length)
     H = int(math.sqrt(length // T))                                       # :97
-    C = vis_f.shape[-1]
-    resized = resize_fn(vis_f[0].reshape(T, H * H, C), H, H, (tgt_size, tgt_size))
-    resized = resized.reshape(1, T * tgt_size * tgt_size, C)
-    merged = torch.cat([sys_f, resized, inst_f], dim=1)                   # :103
-    return merged, position_ids[:, :merged.size(1)], resized.size(1)       # :101, :108
+    C = hidden_states.shape[-1]
+    resized = resize_fn(hidden_states[0, start:start + length].reshape(T, H * H, C), H, H, (tgt_size, tgt_size))
+    resized = resized.reshape(T * tgt_size * tgt_size, C)
+    merged = _splice(hidden_states, start, length, resized)               # :103
+    return merged, _positions_after(position_ids, start, length, merged.size(1)), resized.size(0)       # :101, :108
 
 
 def dycoke_merge(hidden_states, position_ids, start, length, T, ttm_fn, prune_ratio, gather_positions=False):
     """DyCoke stage-1 hook: LLaVA (dycoke_stage1_attn_monkey_patch.py:88-107) truncates position_ids; Qwen2-VL
     (token_merging_qwen2vl_monkey_patch/dycoke_stage1_attn_monkey_patch.py:88-108, gather_positions=True) gathers the 3-D
     mRoPE ids of the kept tokens.  ttm_fn(tokens [T*P, C], T, prune_ratio) -> (tokens, flat ids)."""
-    sys_f, vis_f, inst_f = split_prompt(hidden_states, start, length)
-    end = start + length
-    feat, idx = ttm_fn(vis_f[0], T, prune_ratio)
-    merged = torch.cat([sys_f, feat.unsqueeze(0), inst_f], dim=1)
-    if gather_positions:
-        vis_pos = position_ids[:, :, start:end][:, :, idx]
-        pos = torch.cat([position_ids[:, :, :start], vis_pos, position_ids[:, :, end:]], dim=-1)
-    else:
-        pos = position_ids[:, :merged.size(1)]
-    return merged, pos, idx
+    feat, idx = ttm_fn(hidden_states[0, start:start + length], T, prune_ratio)
+    merged = _splice(hidden_states, start, length, feat)
+    return merged, _positions_after(position_ids, start, length, merged.size(1), idx if gather_positions else None), idx
 
 
 def octree_merge(hidden_states, position_ids, start, length, T, octree_fn, threshold, root_level):
     """Octree hook (octree_attn_monkey_patch.py:87-106): features only, position_ids truncated."""
-    sys_f, vis_f, inst_f = split_prompt(hidden_states, start, length)
     H = int(math.sqrt(length // T))                                       # :96
-    video = _video_view(vis_f[0], T, H, H)
-    feat = octree_fn(video, threshold, root_level)
-    merged = torch.cat([sys_f, feat.unsqueeze(0), inst_f], dim=1)
-    return merged, position_ids[:, :merged.size(1)]
+    video = _video_view(hidden_states[0, start:start + length], T, H, H)
+    merged = _splice(hidden_states, start, length, octree_fn(video, threshold, root_level))
+    return merged, _positions_after(position_ids, start, length, merged.size(1))
 
 
 def quadtree_merge_abl_pos(hidden_states, position_ids, position_embeddings, start, length, T, merge_fn, threshold,
@@ -185,10 +182,9 @@ def quadtree_merge_abl_pos(hidden_states, position_ids, position_embeddings, sta
     pos_emb_ver 0: re-number the shorter sequence (the standard hook); 1: merge the RoPE (cos, sin) rows alongside the features
     (`pos_embs=`); 2: keep every merged token's ORIGINAL position id (gather by the merged index).
     rotary_fn(hidden_states, position_ids) -> (cos, sin).  Returns (hidden_states, position_ids, position_embeddings, idx)."""
-    sys_f, vis_f, inst_f = split_prompt(hidden_states, start, length)
     end = start + length
     H = W = int(math.sqrt(length // T))                                   # :97
-    video = _video_view(vis_f[0], T, H, W)
+    video = _video_view(hidden_states[0, start:end], T, H, W)
     pos_video = None
     if pos_emb_ver > 0:                                                   # :100-104
         pos_video = tuple(_video_view(p[0, start:end], T, H, W) for p in position_embeddings)
@@ -199,17 +195,15 @@ def quadtree_merge_abl_pos(hidden_states, position_ids, position_embeddings, sta
     else:
         feat, _, tlbr = res
     idx = tlbr[:, 0] * (H * W) + tlbr[:, 1] * W + tlbr[:, 2]              # :113-114
-    merged = torch.cat([sys_f, feat.unsqueeze(0), inst_f], dim=1)
+    merged = _splice(hidden_states, start, length, feat)
     n = merged.size(1)
     if pos_emb_ver == 0:                                                  # :120-123
-        position_ids = position_ids[:, :n]
+        position_ids = _positions_after(position_ids, start, length, n)
         position_embeddings = rotary_fn(merged, position_ids)
     elif pos_emb_ver == 1:                                                # :124-128
-        position_embeddings = tuple(torch.cat([p[:, :start], mp.unsqueeze(0), p[:, end:]], dim=1)
-                                    for p, mp in zip(position_embeddings, merged_pos))
-        position_ids = position_ids[:, :n]
+        position_embeddings = tuple(_splice(p, start, length, mp) for p, mp in zip(position_embeddings, merged_pos))
+        position_ids = _positions_after(position_ids, start, length, n)
     elif pos_emb_ver == 2:                                                # :129-135
-        vis_ids = position_ids[:, start:end][:, idx.long()]
-        position_ids = torch.cat([position_ids[:, :start], vis_ids, position_ids[:, end:]], dim=-1)
+        position_ids = _positions_after(position_ids, start, length, n, idx)
         position_embeddings = rotary_fn(merged, position_ids)
     return merged, position_ids, position_embeddings, idx
